@@ -25,6 +25,12 @@ the stream it runs on, inside the timed steps; the JSON line carries, per stage,
 §8(d) algorithmic bytes per transaction, the mean time, the achieved GB/s and its fraction
 of the 8 TB/s HBM peak, plus the HBM traffic rocprofv3 measured for its kernels
 (profiles/pmc_kernels.json) when that file covers them.
+
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+line; everything beyond the headline figure that takes work of its own -- the forest's parity
+check against the saved sklearn output, the isolated per-stage steps, the CPU baseline, the
+variant sweep -- runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step
+computed (dump_outputs) after the timed region.
 """
 import argparse
 import json
@@ -123,7 +129,7 @@ def pmc_table():
         "profiles/pmc_kernels.json" + (f" (rocprofv3 run {d['source']})" if d.get("source") else "")
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -135,7 +141,13 @@ def parse():
     ap.add_argument("--terminals", type=int, default=None, help="override: terminals (as --customers)")
     ap.add_argument("--days", type=int, default=None)
     ap.add_argument("--model", default=os.path.join(ROOT, "bench_assets", "rf100_d20.npz"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the forest's parity check against the saved sklearn output, "
+                         "the isolated per-stage steps (--isolated-steps), the CPU baseline and --sweep-variant")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float64): "
+                         "a fixed seeded sample of the input rows, their probabilities and their 14 feature columns")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-score-rows", type=int, default=200_000,
                     help="rows of the sklearn predict_proba sample in the CPU baseline")
     ap.add_argument("--forest-variant", type=int, default=-1,
@@ -143,9 +155,9 @@ def parse():
     ap.add_argument("--avg-mode", choices=("exact", "scan"), default="exact",
                     help="customer averages: pandas-exact recurrence (default) or float64 prefix sums (SURVEY §7.4)")
     ap.add_argument("--isolated-steps", type=int, default=5,
-                    help="extra steps after the timed region with every stage on one stream (one more untimed "
-                         "first): per-kernel times for the roofline table (median)")
-    ap.add_argument("--sweep-variant", default="", help="comma list of forest variants to time (stderr)")
+                    help="with --full: extra steps after the timed region with every stage on one stream (one more "
+                         "untimed first): per-kernel times for the roofline table (median)")
+    ap.add_argument("--sweep-variant", default="", help="with --full: comma list of forest variants to time (stderr)")
     ap.add_argument("--wide-records", action="store_true",
                     help="terminal count records in the 24-byte form (FraudPipeline(compact_records=False); "
                          "default: the 16-byte compact form)")
@@ -160,7 +172,12 @@ def parse():
                          "GPU per rank); the line is marked \"rehearsal\" and its timing is not a measurement")
     ap.add_argument("--sharded", action="store_true",
                     help="run the multi-GPU (RCCL all-to-all) path even at 1 GPU (measures its overhead)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.sweep_variant and not args.full:
+        ap.error("--sweep-variant is part of --full")
+    return args
 
 
 # BASELINE.json configs: [1] = 50k / 100k / 183 days on one GPU, [3] = 1M / 2M / 365 days on 8
@@ -397,6 +414,53 @@ def cpu_baseline(data, arrays, mean, scale, check_X, check_proba, score_rows):
             "host": info}
 
 
+DUMP_ROWS = 1 << 18  # rows of the --dump-outputs sample: 16 float64 per row, 32 MiB in all
+DUMP_SEED = 20240229
+
+
+def dump_outputs(out_dir, proba, rows_out, n_slots):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step -- proba
+    (input row order) and the featurized table rows_out -- for a fixed seeded sample of this
+    rank's input rows (all of them when there are at most DUMP_ROWS), as float64 .npy files:
+      rows.npy      [m]      the sampled input row indices (ascending),
+      proba.npy     [m]      their probabilities,
+      features.npy  [m, 14]  their feature columns in input_features order (TX_DURING_WEEKEND,
+                             TX_DURING_NIGHT, then per window count and average of the customer
+                             and count and risk of the terminal); absent with --emit-features none.
+    The table is read by input row whichever order it was written in (a slot-order table through
+    its row column), so two builds that place rows in different slots still compare."""
+    import numpy as np
+    import torch
+
+    from fdx import ops
+
+    n = proba.numel()
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, False))
+    idx = torch.from_numpy(rows).to(proba.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "proba.npy"), proba[idx].cpu().numpy().astype(np.float64))
+    if rows_out is None:
+        return
+    if isinstance(rows_out, ops.FeatureRecords):  # records by input row
+        col, at = rows_out.columns(), idx
+    else:  # columns by scoring slot: row[slot] = the input row (-1: padding)
+        col = rows_out.columns(n_slots)
+        slot_row = col["row"].long()
+        slots = torch.nonzero(slot_row >= 0).squeeze(1)
+        slot_of = torch.full((n,), -1, dtype=torch.int64, device=proba.device)
+        slot_of[slot_row[slots]] = slots
+        at = slot_of[idx]
+        if int(at.min()) < 0:
+            raise SystemExit("--dump-outputs: a sampled input row has no slot in the featurized table")
+    pick = lambda c: c[..., at].to(torch.float64)  # noqa: E731
+    F = [pick(col["weekend"]), pick(col["night"])]
+    for half, val in (("cust_nb", "cust_avg"), ("term_nb", "term_risk")):
+        for w in range(3):
+            F += [pick(col[half][w]), pick(col[val][w])]
+    np.save(os.path.join(out_dir, "features.npy"), torch.stack(F, dim=1).cpu().numpy())
+
+
 def rehearse_host_collectives():
     """--rehearse-one-gpu: the exchange's two collectives (fdx.distributed.all_to_all_split_pairs
     and alltoallv, module-level for this) copy their device buffers through host memory and run
@@ -475,10 +539,11 @@ def main():
     if args.forest_variant >= 0:
         forest.set_variant(args.forest_variant)
     T = lambda a, d: torch.from_numpy(np.ascontiguousarray(a)).to(dev, d)  # noqa: E731
-    # sanity: the GPU forest reproduces sklearn on the held-out sample saved with the model
-    got = forest.predict(T(check_X, torch.float64)).cpu().numpy()
-    if not np.array_equal(got, check_proba):
-        raise SystemExit("forest parity check against sklearn failed")
+    if args.full:
+        # sanity: the GPU forest reproduces sklearn on the held-out sample saved with the model
+        got = forest.predict(T(check_X, torch.float64)).cpu().numpy()
+        if not np.array_equal(got, check_proba):
+            raise SystemExit("forest parity check against sklearn failed")
 
     ts, cust, term, amt, fr = g["ts"], g["customer"], g["terminal"], g["amount"], g["fraud"]
     pipe = FraudPipeline(forest=forest, avg_mode=args.avg_mode, compact_records=not args.wide_records)
@@ -565,8 +630,10 @@ def main():
     else:
         n_total = n_local
 
-    iso_all = []  # per-kernel times: every stage alone on the GPU (after the timed region)
-    if marks_all and args.isolated_steps > 0 and not (world > 1 or args.sharded):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proba, rows_out, pipe.last_slots)
+    iso_all = []  # per-kernel times: every stage alone on the GPU (after the timed region; --full)
+    if args.full and marks_all and args.isolated_steps > 0 and not (world > 1 or args.sharded):
         # one untimed step in this mode first: its buffers come from the caller stream's pool,
         # which the overlapped steps (on the pipeline's own streams) never warmed -- the first
         # such step absorbs that pool's allocations (BENCH_r03: 5.65 / 7.57 / 7.92 ms "isolated"
@@ -601,6 +668,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(dt / args.steps * 1e3, 3),
         "higher_is_better": True,
         "scaling": wl["scaling"],
@@ -688,7 +756,8 @@ def main():
         out["kernels"] = {"per_stage": table, "per_unit": krows, "stage_sum_ms": round(step_ms, 3),
                           "streams": "rekey_terminal + terminal_windows run on a side stream, concurrently with the "
                                      "customer stages, so stage_sum_ms (of ms_in_step) exceeds ms_per_step by the "
-                                     "overlap; ms = ms_isolated: the same stages in extra steps with every stage on "
+                                     "overlap; without --full ms = ms_in_step; with it "
+                                     "ms = ms_isolated: the same stages in extra steps with every stage on "
                                      "one stream (no concurrent kernel; median of --isolated-steps after one untimed step in "
                                      "that mode), the per-kernel durations the rooflines use; an isolated time "
                                      f"above {ISOLATED_MAX_OVER_IN_STEP}x the in-step time is rejected "
@@ -757,10 +826,10 @@ def main():
         # every N > 1 line names the N = 1 run of that same table it scales against (a committed
         # bench line: python bench.py --gpus 1 --workload configs3)
         out["scales_against"] = scale_reference(wl)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         data = {k: g[k].cpu().numpy() for k in ("ts", "customer", "terminal", "amount", "fraud")}
         out["cpu_baseline"] = cpu_baseline(data, arrays, mean, scale, check_X, check_proba, args.cpu_score_rows)
-    if args.sweep_variant and rank == 0 and world == 1 and not args.sharded:
+    if args.full and args.sweep_variant and rank == 0 and world == 1 and not args.sharded:
         # each variant: one full untimed pipeline pass (the prepared row format depends on
         # the layout), bit-equality of proba against the default, one untimed and 5 timed
         # traversals; the whole list twice (the first variant timed after the bench loop read

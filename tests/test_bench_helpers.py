@@ -91,6 +91,79 @@ def test_stage_table_medians_and_rejects_inflated_isolated_times():
     assert b.stage_table(in_step, None, stages)[0]["ms"] == 0.95
 
 
+def test_full_gates_the_extra_legs():
+    """A plain run is the timed steps only; --sweep-variant belongs to --full, --steps counts
+    timed steps (at least one)."""
+    import pytest
+
+    b = _bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    assert b.parse(["--full", "--sweep-variant", "1,2", "--dump-outputs", "d"]).dump_outputs == "d"
+    for bad in (["--sweep-variant", "1"], ["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            b.parse(bad)
+
+
+def _filled_table(ops, n, slot_of_row, cap):
+    """A FeatureTable (host memory) whose slot slot_of_row[r] holds row r with features f(r)."""
+    import torch
+
+    t = ops.FeatureTable(cap, torch.device("cpu"))
+    t.buf.zero_()
+    col = t.columns()
+    col["row"].fill_(-1)
+    s = torch.from_numpy(slot_of_row)
+    r = torch.arange(n)
+    col["row"][s] = r.int()
+    for w in range(3):
+        col["cust_nb"][w][s] = (r * 3 + w).int()
+        col["term_nb"][w][s] = (r * 5 + w).int()
+        col["cust_avg"][w][s] = r.double() + 0.25 * w
+        col["term_risk"][w][s] = 1.0 / (r.double() + 1 + w)
+    col["weekend"][s] = (r % 2).to(torch.uint8)
+    col["night"][s] = (r % 3 == 0).to(torch.uint8)
+    return t
+
+
+def _want_features(rows):
+    r = rows.astype(np.float64)
+    cols = [rows % 2, rows % 3 == 0]
+    for nb, val in ((lambda w: r * 3 + w, lambda w: r + 0.25 * w), (lambda w: r * 5 + w, lambda w: 1.0 / (r + 1 + w))):
+        for w in range(3):
+            cols += [nb(w), val(w)]
+    return np.column_stack(cols).astype(np.float64)
+
+
+def test_dump_outputs_reads_the_table_by_input_row(tmp_path):
+    """--dump-outputs: float64 .npy files, rows ascending, proba and the 14 feature columns of those
+    input rows whatever slot the table holds them in; the same seeded sample on every call."""
+    import torch
+
+    from fdx import ops
+
+    b = _bench()
+    n, cap = 1000, 1152
+    slot_of_row = np.random.default_rng(5).permutation(1100)[:n]
+    table = _filled_table(ops, n, slot_of_row, cap)
+    proba = torch.arange(n, dtype=torch.float64) / n
+    b.dump_outputs(str(tmp_path / "all"), proba, table, 1100)
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in ("rows", "proba", "features")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    np.testing.assert_array_equal(got["rows"], np.arange(n))
+    np.testing.assert_array_equal(got["proba"], proba.numpy())
+    np.testing.assert_array_equal(got["features"], _want_features(np.arange(n)))
+    b.DUMP_ROWS = 64  # a larger output: a fixed sample
+    b.dump_outputs(str(tmp_path / "s1"), proba, table, 1100)
+    b.dump_outputs(str(tmp_path / "s2"), proba, None, 0)
+    rows = np.load(tmp_path / "s1" / "rows.npy")
+    assert rows.shape == (64,) and (np.diff(rows) > 0).all() and rows.max() < n
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
+    assert not (tmp_path / "s2" / "features.npy").exists()
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "proba.npy"), rows / n)
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "features.npy"), _want_features(rows.astype(np.int64)))
+
+
 def test_bench_stream_splits_configs4_state_over_ranks():
     """bench_stream.py --gpus N: the 1M / 2M-key state of configs[4] split over the ranks --
     contiguous customer ranges covering every id once, every rank with all terminal ids."""

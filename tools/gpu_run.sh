@@ -3,7 +3,7 @@
 # usage: bash tools/gpu_run.sh <tag> <step> [<step> ...]
 #   tests[=<pytest selection>]   pytest -m gpu (default: tests)
 #   smoke                        __graft_entry__.smoke()
-#   bench[=<bench.py args>]      one bench.py line  -> <tag>_bench.json
+#   bench[=<bench.py args>]      one bench.py line (--full among the args: CPU baseline, isolated stage times)
 #   trace[=<bench.py args>]      rocprofv3 kernel trace + stats of bench.py -> <tag>_trace/
 #   pmc=<counters>[@<args>]      one rocprofv3 --pmc pass of bench.py -> <tag>_pmc_<n>/
 #   forest[=<bench_forest args>] bench_forest.py (configs[2])
