@@ -528,6 +528,8 @@ int fdx_forest_prepare_reply(fdx_forest forest, const int64_t *reply_d, const in
                                    grouped_compact; n_windows = 3, 16-byte aligned)          */
 #define FDX_PREP_FLAG_CLEARED 8 /* the workspace's NaN flag was cleared by fdx_forest_clear_flag
                                    (earlier, e.g. on another stream): no clearing memset here   */
+#define FDX_PREP_INDEX64 16     /* the row kernel's 64-bit slot arithmetic even where n fits 32 bits
+                                   (what n near 2^31 takes; same results -- for tests and A/B)   */
 /* Clears the NaN flag of a forest workspace sized for n rows (a 4-byte memset on `stream`): with
  * FDX_PREP_FLAG_CLEARED, the prepare call that follows skips its own clearing -- the scoring step
  * enqueues this off its critical path (fdx.pipeline). */

@@ -671,7 +671,13 @@ __device__ __forceinline__ void decode_tw(const int64_t *rec, PrepRow &L) {
     }
 }
 
-template <int EMIT, bool COMPACT, bool TINV>
+// I32: the loop's slot bookkeeping in 32-bit wave-uniform scalars (the host takes it whenever n and
+// three sweeps of the grid past it fit an int32).  With the lane's slot and the grid stride as
+// 64-bit VGPR values the kernel, at its 128-VGPR limit, spilled the stride to scratch and reloaded
+// it at the top of every row: the reload's s_waitcnt vmcnt(0) waited there for the previous row's
+// stores and for the prefetched loads -- the wait the notes above are about (1.195 -> 1.147 ms in
+// step at config 2, profiles/r07_assembly_scalar_ab.txt).  false: the 64-bit form, for n beyond.
+template <int EMIT, bool COMPACT, bool TINV, bool I32>
 __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
     const int64_t *__restrict__ cts, const double *__restrict__ camt, const int32_t *__restrict__ cnb,
     const double *__restrict__ cval, const int32_t *__restrict__ cust_perm, const int32_t *__restrict__ term_inv,
@@ -739,13 +745,21 @@ __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
     // wave runs each iteration, so the quads of k_seg_count_quad stay whole; lanes past n and
     // padding slots compute on defined dummies and store the zero row / nothing
     const int lane = threadIdx.x & (kWave - 1);
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // I32: sb = the wave's first slot (its lanes' slots: sb + lane), sstride = the grid's sweep, n32 = n
+    const int32_t n32 = I32 ? (int32_t)n : 0;
+    const int32_t sstride = I32 ? (int32_t)(gridDim.x * (uint32_t)kW3Block) : 0;
+    int32_t sb = I32 ? (int32_t)(blockIdx.x * (uint32_t)kW3Block) +
+                           __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6)) * kWave
+                     : 0;
+    int64_t i = I32 ? (int64_t)(sb + lane) : (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // the lane's slot m rows ahead
+    auto ahead = [&](int m) -> int64_t { return I32 ? (int64_t)(sb + m * sstride + lane) : i + m * stride; };
     PrepRow cur;
     {
         const int32_t r0 = row_of(i);
         load(i, r0, rec_of(r0), cur);
     }
-    int32_t r1 = row_of(i + stride), r2 = row_of(i + 2 * stride);  // slots one and two ahead
+    int32_t r1 = row_of(ahead(1)), r2 = row_of(ahead(2));  // slots one and two ahead
     int64_t q1 = rec_of(r1);
     // one row per call; the loop below runs it with its first iteration peeled, so
     // that the loop header is reached only in the steady state: entered straight from the
@@ -755,10 +769,10 @@ __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
     auto row_iter = [&]() {
         settle(i, cur);
         PrepRow nxt;
-        load(i + stride, r1, q1, nxt);  // next row's loads in flight during this row
-        q1 = rec_of(r2);                // (r2 arrived during the previous row)
+        load(ahead(1), r1, q1, nxt);  // next row's loads in flight during this row
+        q1 = rec_of(r2);              // (r2 arrived during the previous row)
         r1 = r2;
-        r2 = row_of(i + 3 * stride);
+        r2 = row_of(ahead(3));
         const bool live = i < n && cur.r >= 0;
         bool we, ni;
         day_flags(cur.t, flags_mode, we, ni);
@@ -909,12 +923,16 @@ __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
                           : make_uint4(0, 0, 0, 0);
         }
         cur = nxt;
+        if constexpr (I32) {
+            sb += sstride;
+            i = (int64_t)(sb + lane);
+        } else {
+            i += stride;
+        }
     };
-    if (i - lane < n) {  // (the first iteration peeled)
-        row_iter();
-        i += stride;
-    }
-    for (; i - lane < n; i += stride) row_iter();
+    auto more = [&]() -> bool { return I32 ? sb < n32 : i - lane < n; };
+    if (more()) row_iter();  // (the first iteration peeled)
+    while (more()) row_iter();
 }
 
 
@@ -1194,8 +1212,9 @@ extern "C" int fdx_forest_prepare_grouped_rows(fdx_forest F, int64_t n, int32_t 
                 3 + 4 * n_windows);
     if (n == 0) return FDX_OK;
     FDX_REQUIRE(cust_ts_d && cust_amount_d && cust_nb_d && cust_avg_d && term_rec_d, "null pointer");
-    FDX_REQUIRE((cust_val_is_sum & ~13) == 0,
-                "cust_val_is_sum: FDX_PREP_VAL_IS_SUM | FDX_PREP_TERM_COMPACT | FDX_PREP_FLAG_CLEARED only");
+    FDX_REQUIRE((cust_val_is_sum & ~29) == 0,
+                "cust_val_is_sum: FDX_PREP_VAL_IS_SUM | FDX_PREP_TERM_COMPACT | FDX_PREP_FLAG_CLEARED | "
+                "FDX_PREP_INDEX64 only");
     FDX_REQUIRE(!(cust_val_is_sum & 4) || (n_windows == 3 && ((uintptr_t)term_rec_d & 15) == 0),
                 "compact terminal records: W = 3 and a 16-byte aligned record array");
     float *z;
@@ -1206,13 +1225,20 @@ extern "C" int fdx_forest_prepare_grouped_rows(fdx_forest F, int64_t n, int32_t 
     hipStream_t st = as_stream(stream);
     if (!(cust_val_is_sum & FDX_PREP_FLAG_CLEARED)) FDX_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
     cust_val_is_sum &= ~FDX_PREP_FLAG_CLEARED;
+    const bool index64 = (cust_val_is_sum & FDX_PREP_INDEX64) != 0;
+    cust_val_is_sum &= ~FDX_PREP_INDEX64;
     const unsigned grid = stream_grid(n, 256);
     const RankTab rt = rank_tab(F);
     if (rank_mode(F) && n_windows == 3 && rt.rat && rt.etab) {
+#define FDX_ZFILL_W3_I(E, C, T, I)                                                                                \
+    hipLaunchKernelGGL((k_zfill_grouped_w3<E, C, T, I>), dim3(grid_w3), dim3(kW3Block), 0, st, cust_ts_d,          \
+                       cust_amount_d, cust_nb_d, cust_avg_d, cust_perm_d, term_inv_d, term_rec_d, n, flags_mode,    \
+                       cust_val_is_sum, F->mean_d, F->scale_d, (void *)z, flag, rt,                                 \
+                       reinterpret_cast<char *>(rows_out_d), out_cap)
 #define FDX_ZFILL_W3(E, C, T)                                                                                     \
-    hipLaunchKernelGGL((k_zfill_grouped_w3<E, C, T>), dim3(grid_w3), dim3(kW3Block), 0, st, cust_ts_d, cust_amount_d, \
-                       cust_nb_d, cust_avg_d, cust_perm_d, term_inv_d, term_rec_d, n, flags_mode, cust_val_is_sum,   \
-                       F->mean_d, F->scale_d, (void *)z, flag, rt, reinterpret_cast<char *>(rows_out_d), out_cap)
+    do {                                                                                                          \
+        if (i32) FDX_ZFILL_W3_I(E, C, T, true); else FDX_ZFILL_W3_I(E, C, T, false);                              \
+    } while (0)
 #define FDX_ZFILL_W3_E(E)                                                                                         \
     do {                                                                                                          \
         if (cust_val_is_sum & 4) {                                                                                \
@@ -1222,6 +1248,8 @@ extern "C" int fdx_forest_prepare_grouped_rows(fdx_forest F, int64_t n, int32_t 
         }                                                                                                         \
     } while (0)
         const unsigned grid_w3 = stream_grid(n, kW3Block, device_cus());
+        // (the 32-bit loop looks three sweeps of the grid past n)
+        const bool i32 = !index64 && n + 4 * (int64_t)grid_w3 * kW3Block <= (int64_t)INT32_MAX;
         if (!rows_out_d)
             FDX_ZFILL_W3_E(0);
         else if (rows_order == FDX_ROWS_SLOT_ORDER)
@@ -1230,6 +1258,7 @@ extern "C" int fdx_forest_prepare_grouped_rows(fdx_forest F, int64_t n, int32_t 
             FDX_ZFILL_W3_E(FDX_ROWS_INPUT_ORDER);
 #undef FDX_ZFILL_W3_E
 #undef FDX_ZFILL_W3
+#undef FDX_ZFILL_W3_I
         FDX_LAUNCHED("k_zfill_grouped_w3");
         return FDX_OK;
     }

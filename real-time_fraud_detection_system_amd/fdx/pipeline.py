@@ -65,6 +65,9 @@ class FraudPipeline:
     # the step's intermediates in the pipeline's own arena (ops.Arena; 0: torch's caching allocator
     # per call, as before round 6 -- tools/step_ab.py measures the two)
     use_arena = 1
+    # 1: the row assembly with its 64-bit slot arithmetic (what it ran before it kept the loop's
+    # bookkeeping in 32-bit scalars; tools/step_ab.py measures the two -- DESIGN §4)
+    assembly_index64 = 0
     # how long the host polls for the layout plan's slot count before a blocking wait: the plan of
     # step k lands only after step k - 1's forest (6.6 ms at configs[1]) when steps are queued back
     # to back, and a blocking hipEventSynchronize woke up ~150 us after it (profiles/r06t trace: plan
@@ -297,7 +300,8 @@ class FraudPipeline:
                 with torch.cuda.stream(tail):
                     ops.forest_prepare_grouped(self.forest, self.flags_mode, lay.its, lay.iamt, inb, isum, lay.irow,
                                                None, trec, ws, tail, n=lay.n_slots, val_is_sum=True,
-                                               term_compact=compact, rows_out=rows_out, flag_cleared=tail is not main)
+                                               term_compact=compact, rows_out=rows_out, flag_cleared=tail is not main,
+                                               index64=bool(self.assembly_index64))
                     mk("assemble_rows", tail)
                     ops.forest_traverse_perm(self.forest, lay.n_slots, ws, proba, lay.irow, tail)
                     mk("forest_traverse", tail)
