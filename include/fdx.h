@@ -117,6 +117,21 @@ int fdx_customer_layout_fill_starts_grouped(const int64_t *seg_off_d, int64_t n_
                                             int32_t n_windows, const int32_t *sorder_d, const uint32_t *goff_d,
                                             int64_t n_slots, int64_t *its_d, double *iamt_d, int32_t *irow_d,
                                             int32_t *starts_d, void *stream);
+/* The fill over fdx_rekey_payload_narrow's outputs: gts_d / gamount_d hold whichever form
+ * *narrow_flag_d (device int32) names (narrow_mask: that re-key's, not 0), ts_base_d is that
+ * re-key's ts_ns_d (row 0 = the base of the seconds).  its_d, iamt_d, irow_d and starts_d are
+ * written bit for bit as fdx_customer_layout_fill_starts_grouped writes them from the 8-byte
+ * columns.  One launch: each block loads the flag once and takes the 4-byte or the 8-byte
+ * loads, uniformly; a narrow element is widened where it is loaded (ts_base_d[0] + s * 1e9,
+ * (double)c / 100.0), so the staged timestamps and the start searches are the wide form's.
+ * The windows must be whole seconds (FDX_E_INVALID; fdx_narrow_windows_ok). */
+int fdx_customer_layout_fill_starts_grouped_narrow(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
+                                                   const void *gts_d, const void *gamount_d,
+                                                   const int64_t *window_ns, int32_t n_windows,
+                                                   const int32_t *sorder_d, const uint32_t *goff_d, int64_t n_slots,
+                                                   int64_t *its_d, double *iamt_d, int32_t *irow_d, int32_t *starts_d,
+                                                   const int32_t *narrow_flag_d, int32_t narrow_mask,
+                                                   const int64_t *ts_base_d, void *stream);
 
 /* fdx_customer_layout_starts over GROUPED ts / amount (fdx_rekey_payload outputs: row j of
  * the grouping is gts_d[j], gamount_d[j]) -- the layout then reads every segment as a
@@ -235,6 +250,17 @@ int fdx_terminal_windows_grouped_compact(const int64_t *gts_d, const uint8_t *gf
                                          const int64_t *seg_off_d, int64_t n_seg, int64_t n, int64_t delay_ns,
                                          const int64_t *window_ns, int32_t n_windows, int32_t runs, int64_t *rec_d,
                                          int32_t *scratch_d, void *stream);
+/* fdx_terminal_windows_grouped_compact (n_windows = 3, single-run segments) over
+ * fdx_rekey_payload_narrow's ts output: gts_d holds int32 seconds when *narrow_flag_d == 0 and
+ * the int64 column otherwise.  Each block of the two kernels loads the flag once and takes the
+ * 4-byte or the 8-byte loads, uniformly; seconds are widened to s * 1e9 where they are loaded
+ * (the kernels compare differences of timestamps only, so the common base drops out), and the
+ * records are bit for bit those of fdx_terminal_windows_grouped_compact; closed='right' as
+ * before.  The delay and the windows must be whole seconds (FDX_E_INVALID otherwise). */
+int fdx_terminal_windows_grouped_narrow(const void *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
+                                        const int64_t *seg_off_d, int64_t n_seg, int64_t n, int64_t delay_ns,
+                                        const int64_t *window_ns, int32_t n_windows, int64_t *rec_d,
+                                        int32_t *scratch_d, const int32_t *narrow_flag_d, void *stream);
 
 /* ---- a-4: re-key (stable radix sort by key + segment offsets) -------------------------
  * Replaces the regrouping done by pandas groupby('CUSTOMER_ID') / sort_values /
@@ -289,6 +315,43 @@ int fdx_rekey_payload_hist0(const int32_t *keys_d, int64_t n, int32_t key_bits, 
                             const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d, int64_t *seg_off_d,
                             uint64_t *pay0_out_d, uint64_t *pay1_out_d, const void *hist0_d, void *workspace_d,
                             size_t workspace_bytes, void *stream);
+/* The payload re-key in its NARROW form: the two columns the window kernels read travel through
+ * the radix passes as 4 bytes per row instead of 8 whenever that loses nothing.
+ *   ts_ns_d   (stream 0, required)  -> int32 seconds relative to ts_ns_d[0] (read on the device).
+ *             Exact iff for every row (ts - ts_ns_d[0]) is a whole number of seconds (1e9 ns) whose
+ *             quotient fits int32; rows out of time order give negative offsets, which is fine.
+ *   amount_d  (stream 1, optional)  -> int32 cents c = rint(a * 100.0).  Exact iff |c| < 2^31 and
+ *             (double)c / 100.0 has the same 64 bits as a -- NaN, +-inf, -0.0 and every non-cent
+ *             value fail.  Consumers rebuild a with that same division: bit-identical by construction.
+ * No pass of its own checks this: the first radix pass reads the 8-byte columns anyway, converts
+ * while it scatters and stores 1 to *narrow_flag_d (device int32, cleared by the call) at the first
+ * value without a narrow form.  One wide launch of the FIRST pass follows the converting one:
+ * its blocks return at once while the flag is clear, and redo the pass on the 8-byte columns when
+ * it is raised (the converting pass itself never returns early).  Every later pass is one kernel
+ * whose blocks load the flag once and move 4-byte or 8-byte streams, uniformly -- so after the call
+ *   *narrow_flag_d == 0: ts_out_d holds int32 [n] seconds, amount_out_d int32 [n] cents;
+ *   *narrow_flag_d != 0: they hold the int64 [n] / float64 [n] columns of fdx_rekey_payload.
+ * Both are buffers of 8 n bytes, and the workspace is fdx_rekey_payload_workspace_size's (the
+ * 4-byte streams alias the 8-byte ones).  perm_d and seg_off_d are the same in both forms.
+ * narrow_mask: which columns to try -- FDX_NARROW_TS | FDX_NARROW_AMOUNT, or FDX_NARROW_TS alone
+ * (amount_d then travels as 8 bytes, unchecked, and amount_out_d is float64 whatever the flag
+ * says: for tables whose amounts are known not to be cents, where trying would cost the fallback
+ * every time), or 0 (the caller's windows or delay are not whole seconds, see
+ * fdx_narrow_windows_ok): the flag is raised from the start and the call is fdx_rekey_payload.
+ * The consumers take the flag: fdx_customer_layout_fill_starts_grouped_narrow and
+ * fdx_terminal_windows_grouped_narrow; each block of their kernels loads it once.
+ * bad_d (optional): as fdx_rekey_payload_checked.  hist0_d (optional): as fdx_rekey_payload_hist0
+ * (then bad_d must be NULL). */
+#define FDX_NARROW_TS 1
+#define FDX_NARROW_AMOUNT 2
+int fdx_rekey_payload_narrow(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys, const uint8_t *flag_d,
+                             const int64_t *ts_ns_d, const double *amount_d, int32_t *perm_d, int64_t *seg_off_d,
+                             void *ts_out_d, void *amount_out_d, int32_t *bad_d, const void *hist0_d,
+                             int32_t *narrow_flag_d, int32_t narrow_mask, void *workspace_d, size_t workspace_bytes,
+                             void *stream);
+/* 1 iff every window and the delay (pass 0 for none) are whole seconds: the narrow consumers
+ * compare int32 seconds, which decides as the nanosecond comparison does only then. */
+int fdx_narrow_windows_ok(const int64_t *window_ns, int32_t n_windows, int64_t delay_ns);
 /* seg_off_d[0..n_keys] from keys sorted ascending (fdx_rekey's seg_off: rows of key k at
  * [seg_off_d[k], seg_off_d[k+1])), one pass over the keys; keys outside [0, n_keys) never put an
  * offset outside [0, n]. */

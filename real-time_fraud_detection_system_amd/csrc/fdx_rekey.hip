@@ -208,12 +208,59 @@ inline unsigned scatter_grid(int64_t n_tiles) { return (unsigned)((n_tiles + 7) 
 // instead of 3 per item (measured on MI355X at config 2: terminal re-key 0.686 -> 0.611 ms,
 // 64-bit argsort 2.43 -> 1.59 ms, customer re-key unchanged; bit-identical,
 // tools/radix_ab.py).  The tile's global digit offsets are staged in LDS once.
-template <typename K, int BITS, int PW>
-__global__ void __launch_bounds__(kBlock) k_radix_scatter(
-    const K *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, int64_t n, int shift, K flip,
-    int64_t n_tiles, const uint32_t *__restrict__ offsets, K *__restrict__ keys_out,
+//
+// scatter_one_tile is the tile's work; k_radix_scatter (one tile per block, 8-byte streams) and
+// k_radix_scatter_narrow (the forms below) are its kernels.
+// PM: the payload form (fdx_rekey_payload_narrow; nflag = its device flag, 0 = narrow holds).
+//   kPayWide       8-byte streams in and out (nflag unused): k_radix_scatter.
+//   kPayConvert    the first pass of the narrow form: reads the 8-byte columns (stream 0 = int64
+//                  timestamps, stream 1 = float64 amounts), writes 4-byte streams (narrow_ts /
+//                  narrow_cents) and raises the flag at the first value that has no exact
+//                  narrow form.  tbase = the timestamps' input column (its row 0 is the base).
+//   kPayWideGated  the first pass's fallback, launched behind kPayConvert: kPayWide, but every
+//                  block returns at once while the flag is clear.  A block has to be given its
+//                  LDS and registers even to return, and beside the customer walk (which fills
+//                  the CUs' LDS) a full grid of such blocks took 140-150 us to drain (r08 trace);
+//                  so this form runs a small grid whose blocks loop over the tiles.
+//   kPayNarrow     a later pass: each block loads the flag once and moves 4-byte streams when
+//                  it is clear, 8-byte streams when it is raised (a uniform branch around the
+//                  loads, the LDS re-order and the stores; keys and values are the same).
+// AMT (the narrow forms): stream 1 goes narrow as well; false: only the timestamps do, and
+// stream 1 stays an 8-byte stream (unchecked) in every pass.
+enum { kPayWide = 0, kPayConvert = 1, kPayNarrow = 2, kPayWideGated = 3 };
+constexpr unsigned kGatedGrid = 2048;  // blocks of a kPayWideGated launch (a multiple of 8)
+constexpr int64_t kNsPerSec = 1000000000LL;
+
+// int32 seconds relative to base, exact iff ts - base is a whole number of seconds that fits
+__device__ __forceinline__ uint32_t narrow_ts(uint64_t bits, int64_t base, bool *ok) {
+    int64_t d;
+    const bool ov = __builtin_sub_overflow((int64_t)bits, base, &d);
+    const int64_t q = d / kNsPerSec;
+    *ok = !ov && q * kNsPerSec == d && q == (int64_t)(int32_t)q;
+    return (uint32_t)(int32_t)q;
+}
+
+// int32 cents c = rint(a * 100), exact iff |c| < 2^31 and (double)c / 100.0 has a's 64 bits
+// (NaN, +-inf, -0.0 and every non-cent value fail); the consumers rebuild a with that division
+__device__ __forceinline__ uint32_t narrow_cents(uint64_t bits, bool *ok) {
+    const double a = __longlong_as_double((long long)bits);
+    const double c = rint(a * 100.0);
+    const bool fits = fabs(c) < 2147483648.0;  // (false for NaN)
+    const int32_t ci = fits ? (int32_t)c : 0;
+    *ok = fits && (uint64_t)__double_as_longlong((double)ci / 100.0) == bits;
+    return (uint32_t)ci;
+}
+
+template <typename K, int BITS, int PW, int PM, bool AMT>
+__device__ __forceinline__ void scatter_one_tile(
+    const int64_t tile, const K *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, int64_t n, int shift,
+    K flip, int64_t n_tiles, const uint32_t *__restrict__ offsets, K *__restrict__ keys_out,
     uint32_t *__restrict__ vals_out, const uint8_t *__restrict__ flag_in, const uint64_t *__restrict__ p0_in,
-    const uint64_t *__restrict__ p1_in, uint64_t *__restrict__ p0_out, uint64_t *__restrict__ p1_out) {
+    const uint64_t *__restrict__ p1_in, uint64_t *__restrict__ p0_out, uint64_t *__restrict__ p1_out,
+    int32_t *nflag, const int64_t *__restrict__ tbase) {
+    static_assert(PM == kPayWide || PW > 0, "the narrow forms are payload forms");
+    bool nar = false;  // kPayNarrow: the streams are 4-byte ones (uniform)
+    if constexpr (PM == kPayNarrow) nar = *nflag == 0;
     constexpr int kBins = 1 << BITS, kPer = kBins / kBlock;
     static_assert(kBins % kBlock == 0, "digit bins must be a multiple of the block");
     constexpr int kWaveSpan = kTile / kWavesPerBlock;  // 1,024 input positions per wave
@@ -225,8 +272,6 @@ __global__ void __launch_bounds__(kBlock) k_radix_scatter(
     uint32_t *s_val = s_kv + kKeyWords * kTile;
 
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-    const int64_t tile = scatter_tile(n_tiles);
-    if (tile >= n_tiles) return;
     const int64_t base = tile * kTile;
     const int64_t wbase = base + (int64_t)wv * kWaveSpan + lane;  // + r * 64: item r of this lane
     for (int d = tid; d < kBins; d += kBlock)
@@ -285,10 +330,28 @@ __global__ void __launch_bounds__(kBlock) k_radix_scatter(
     // no branch); the loads of stream 0 go out behind the key re-order and those of stream q + 1
     // while stream q is re-ordered (r03: each after the previous phase's stores, or stream 0 with
     // the keys -- 170 VGPRs -- measured slower)
-    uint64_t pv[PW > 0 ? kItems : 1];
-    auto load_pay = [&](const uint64_t *pin) {
+    uint64_t pv[PW > 0 ? kItems : 1];  // (a 4-byte element in the low word)
+    bool inexact = false;  // kPayConvert: this lane met a value without a narrow form
+    auto load_pay = [&](const uint64_t *pin, auto qc) {
+        constexpr int q = decltype(qc)::value;
+        constexpr bool can = q == 0 || AMT;  // stream q has a narrow form in this launch
+        if (PM == kPayNarrow && can && nar) {
+            const uint32_t *pin32 = reinterpret_cast<const uint32_t *>(pin);
 #pragma unroll
-        for (int r = 0; r < kItems; ++r) pv[r] = pin[min(wbase + (int64_t)r * kWave, n - 1)];
+            for (int r = 0; r < kItems; ++r) pv[r] = pin32[min(wbase + (int64_t)r * kWave, n - 1)];
+        } else {
+#pragma unroll
+            for (int r = 0; r < kItems; ++r) pv[r] = pin[min(wbase + (int64_t)r * kWave, n - 1)];
+            if constexpr (PM == kPayConvert && can) {
+                const int64_t b0 = q == 0 ? tbase[0] : 0;
+#pragma unroll
+                for (int r = 0; r < kItems; ++r) {
+                    bool ok;
+                    pv[r] = q == 0 ? narrow_ts(pv[r], b0, &ok) : narrow_cents(pv[r], &ok);
+                    inexact |= !ok;
+                }
+            }
+        }
     };
 #pragma unroll
     for (int r = 0; r < kItems; ++r) {
@@ -357,7 +420,7 @@ __global__ void __launch_bounds__(kBlock) k_radix_scatter(
             s_val[p] = val[r];
         }
     }
-    if constexpr (PW > 0) load_pay(p0_in);
+    if constexpr (PW > 0) load_pay(p0_in, std::integral_constant<int, 0>{});
     __syncthreads();
     const int64_t tcnt = std::min<int64_t>(kTile, n - base);
     int32_t dsts[kItems];  // destination of tile position tid + j * kBlock
@@ -373,22 +436,79 @@ __global__ void __launch_bounds__(kBlock) k_radix_scatter(
         }
     }
     if constexpr (PW > 0) {
-        uint64_t *s_pay = reinterpret_cast<uint64_t *>(s_kv);
-#pragma unroll
-        for (int q = 0; q < PW; ++q) {
-            uint64_t *pout = q == 0 ? p0_out : p1_out;
+        auto stream_as = [&](auto qc, auto po) {
+            constexpr int q = decltype(qc)::value;
+            using PO = decltype(po);  // the stream's element on the way out
+            PO *s_pay = reinterpret_cast<PO *>(s_kv);
+            PO *pout = reinterpret_cast<PO *>(q == 0 ? p0_out : p1_out);
             __syncthreads();  // the previous contents of the LDS slots are consumed
 #pragma unroll
             for (int r = 0; r < kItems; ++r)
-                if (wbase + (int64_t)r * kWave < n) s_pay[pos[r]] = pv[r];
-            if (q + 1 < PW) load_pay(p1_in);
+                if (wbase + (int64_t)r * kWave < n) s_pay[pos[r]] = (PO)pv[r];
+            if constexpr (q + 1 < PW) load_pay(p1_in, std::integral_constant<int, 1>{});
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < kItems; ++j) {
                 const int p = tid + j * kBlock;
                 if (p < tcnt) pout[dsts[j]] = s_pay[p];
             }
+        };
+        auto stream = [&](auto qc) {
+            constexpr bool can = decltype(qc)::value == 0 || AMT;
+            if constexpr (PM == kPayConvert && can) {
+                stream_as(qc, uint32_t{});
+            } else if constexpr (PM == kPayNarrow && can) {
+                if (nar) stream_as(qc, uint32_t{});  // (uniform)
+                else stream_as(qc, uint64_t{});
+            } else {
+                stream_as(qc, uint64_t{});
+            }
+        };
+        stream(std::integral_constant<int, 0>{});
+        if constexpr (PW > 1) stream(std::integral_constant<int, 1>{});
+        if constexpr (PM == kPayConvert) {
+            if (inexact) *nflag = 1;  // (a vector store per lane that met one; all store the same 1)
         }
+    }
+}
+
+template <typename K, int BITS, int PW>
+__global__ void __launch_bounds__(kBlock) k_radix_scatter(
+    const K *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, int64_t n, int shift, K flip,
+    int64_t n_tiles, const uint32_t *__restrict__ offsets, K *__restrict__ keys_out,
+    uint32_t *__restrict__ vals_out, const uint8_t *__restrict__ flag_in, const uint64_t *__restrict__ p0_in,
+    const uint64_t *__restrict__ p1_in, uint64_t *__restrict__ p0_out, uint64_t *__restrict__ p1_out) {
+    const int64_t tile = scatter_tile(n_tiles);
+    if (tile >= n_tiles) return;
+    scatter_one_tile<K, BITS, PW, kPayWide, true>(tile, keys_in, vals_in, n, shift, flip, n_tiles, offsets, keys_out,
+                                                  vals_out, flag_in, p0_in, p1_in, p0_out, p1_out, nullptr, nullptr);
+}
+
+// The narrow forms' kernel.  kPayWideGated: a small grid; block b takes the tiles b / 8 + k * gridDim.x / 8
+// of its XCD's range (scatter_tile's mapping, continued), or returns at once while the flag is clear.
+template <typename K, int BITS, int PW, int PM, bool AMT>
+__global__ void __launch_bounds__(kBlock) k_radix_scatter_narrow(
+    const K *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, int64_t n, int shift, K flip,
+    int64_t n_tiles, const uint32_t *__restrict__ offsets, K *__restrict__ keys_out,
+    uint32_t *__restrict__ vals_out, const uint8_t *__restrict__ flag_in, const uint64_t *__restrict__ p0_in,
+    const uint64_t *__restrict__ p1_in, uint64_t *__restrict__ p0_out, uint64_t *__restrict__ p1_out,
+    int32_t *nflag, const int64_t *__restrict__ tbase) {
+    static_assert(PM != kPayWide, "k_radix_scatter is the wide form");
+    if constexpr (PM == kPayWideGated) {
+        if (*nflag == 0) return;  // (uniform: before any barrier)
+        const int64_t per = (n_tiles + 7) / 8;
+        for (int64_t tx = blockIdx.x / 8; tx < per; tx += gridDim.x / 8) {
+            const int64_t tile = (int64_t)(blockIdx.x % 8) * per + tx;
+            if (tile >= n_tiles) return;
+            scatter_one_tile<K, BITS, PW, PM, AMT>(tile, keys_in, vals_in, n, shift, flip, n_tiles, offsets, keys_out,
+                                                   vals_out, flag_in, p0_in, p1_in, p0_out, p1_out, nflag, tbase);
+            __syncthreads();  // the tile's LDS is consumed
+        }
+    } else {
+        const int64_t tile = scatter_tile(n_tiles);
+        if (tile >= n_tiles) return;
+        scatter_one_tile<K, BITS, PW, PM, AMT>(tile, keys_in, vals_in, n, shift, flip, n_tiles, offsets, keys_out,
+                                               vals_out, flag_in, p0_in, p1_in, p0_out, p1_out, nflag, tbase);
     }
 }
 
@@ -553,12 +673,19 @@ size_t sort_ws(int64_t n, SortWs<K> *w, char *base, int pw = 0) {
 // vals_out receives the input row index of each sorted position (| flag << 31 with flag_in);
 // keys_out (optional) the sorted keys; pay_out[q] (PW streams) the payload in sorted order.
 // Returns the buffer that holds the sorted keys.
-template <typename K, int BITS, int PW>
+template <typename K, int BITS, int PW, int PM = kPayWide, bool AMT = true>
 void launch_scatter(const K *kin, const uint32_t *vin, int64_t n, int shift, K flip, int64_t tiles,
                     const uint32_t *hist, K *kout, uint32_t *vout, const uint8_t *flag_in, const uint64_t *const (&pin)[2],
-                    uint64_t *const (&pout)[2], hipStream_t st) {
-    hipLaunchKernelGGL((k_radix_scatter<K, BITS, PW>), dim3(scatter_grid(tiles)), dim3(kBlock), 0, st, kin, vin, n, shift,
-                       flip, tiles, hist, kout, vout, flag_in, pin[0], pin[1], pout[0], pout[1]);
+                    uint64_t *const (&pout)[2], hipStream_t st, int32_t *nflag = nullptr,
+                    const int64_t *tbase = nullptr) {
+    const unsigned grid = PM == kPayWideGated ? std::min(scatter_grid(tiles), kGatedGrid) : scatter_grid(tiles);
+    if constexpr (PM == kPayWide)
+        hipLaunchKernelGGL((k_radix_scatter<K, BITS, PW>), dim3(grid), dim3(kBlock), 0, st, kin, vin, n, shift, flip,
+                           tiles, hist, kout, vout, flag_in, pin[0], pin[1], pout[0], pout[1]);
+    else
+        hipLaunchKernelGGL((k_radix_scatter_narrow<K, BITS, PW, PM, AMT>), dim3(grid), dim3(kBlock), 0, st, kin, vin,
+                           n, shift, flip, tiles, hist, kout, vout, flag_in, pin[0], pin[1], pout[0], pout[1], nflag,
+                           tbase);
 }
 
 // The digit schedule of a `bits`-bit key: passes, and how many leading passes take 9 bits.
@@ -596,10 +723,13 @@ template <typename K>
 int radix_sort(const K *keys, int64_t n, int bits, K flip, K *keys_out, uint32_t *vals_out,
                const SortWs<K> &w, hipStream_t st, const K **sorted, int pw = 0, const uint8_t *flag_in = nullptr,
                const uint64_t *const *pay_in = nullptr, uint64_t *const *pay_out = nullptr, uint64_t key_limit = 0,
-               int32_t *bad = nullptr, const uint32_t *hist0 = nullptr) {
+               int32_t *bad = nullptr, const uint32_t *hist0 = nullptr, int32_t *nflag = nullptr,
+               bool namt = true) {
     const int64_t tiles = ceil_div(n, kTile);
     int passes, n9;
     digit_plan(bits, &passes, &n9);
+    // nflag (pw >= 1, passes >= 1): the narrow payload form, see k_radix_scatter (namt: stream 1 too)
+    const int64_t *tbase = nflag ? reinterpret_cast<const int64_t *>(pay_in[0]) : nullptr;
     const K *kin = keys;
     const uint32_t *vin = nullptr;  // identity on the first pass
     const uint64_t *pin[2] = {pw > 0 ? pay_in[0] : nullptr, pw > 1 ? pay_in[1] : nullptr};
@@ -638,13 +768,40 @@ int radix_sort(const K *keys, int64_t n, int bits, K flip, K *keys_out, uint32_t
             if (rc) return rc;
         }
         const uint8_t *fl = p == 0 ? flag_in : nullptr;
-#define FDX_SCATTER(B, PWV) \
-    launch_scatter<K, B, PWV>(kin, vin, n, shift, flip, tiles, htab, kout, vout, fl, pin, pout, st)
-        if (dbits == 9) {
-            if (pw == 2) FDX_SCATTER(9, 2); else if (pw == 1) FDX_SCATTER(9, 1); else FDX_SCATTER(9, 0);
-        } else {
-            if (pw == 2) FDX_SCATTER(kRadixBits, 2); else if (pw == 1) FDX_SCATTER(kRadixBits, 1); else FDX_SCATTER(kRadixBits, 0);
+#define FDX_SCATTER(B, PWV, PMV) \
+    launch_scatter<K, B, PWV, PMV>(kin, vin, n, shift, flip, tiles, htab, kout, vout, fl, pin, pout, st, nflag, tbase)
+#define FDX_SCATTER_N(B, PMV)                                                                                   \
+    do {                                                                                                        \
+        if (pw == 2 && namt)                                                                                    \
+            FDX_SCATTER(B, 2, PMV);                                                                             \
+        else if (pw == 2)                                                                                       \
+            launch_scatter<K, B, 2, PMV, false>(kin, vin, n, shift, flip, tiles, htab, kout, vout, fl, pin, pout, st, \
+                                                nflag, tbase);                                                  \
+        else                                                                                                    \
+            FDX_SCATTER(B, 1, PMV);                                                                             \
+    } while (0)
+        if constexpr (std::is_same_v<K, uint32_t>) {
+            // the first pass converts, and its wide fallback follows (it returns at once unless the
+            // flag was raised; both write the same buffers -- the 4-byte streams alias the 8-byte
+            // ones -- and the same keys and values); a later pass takes the form the flag names
+            if (nflag) {
+                if (p == 0) {
+                    if (dbits == 9) FDX_SCATTER_N(9, kPayConvert); else FDX_SCATTER_N(kRadixBits, kPayConvert);
+                    FDX_LAUNCHED("k_radix_scatter");
+                    if (dbits == 9) FDX_SCATTER_N(9, kPayWideGated); else FDX_SCATTER_N(kRadixBits, kPayWideGated);
+                } else {
+                    if (dbits == 9) FDX_SCATTER_N(9, kPayNarrow); else FDX_SCATTER_N(kRadixBits, kPayNarrow);
+                }
+            }
         }
+        if (!nflag) {
+            if (dbits == 9) {
+                if (pw == 2) FDX_SCATTER(9, 2, kPayWide); else if (pw == 1) FDX_SCATTER(9, 1, kPayWide); else FDX_SCATTER(9, 0, kPayWide);
+            } else {
+                if (pw == 2) FDX_SCATTER(kRadixBits, 2, kPayWide); else if (pw == 1) FDX_SCATTER(kRadixBits, 1, kPayWide); else FDX_SCATTER(kRadixBits, 0, kPayWide);
+            }
+        }
+#undef FDX_SCATTER_N
 #undef FDX_SCATTER
         FDX_LAUNCHED("k_radix_scatter");
         kin = kout;
@@ -708,7 +865,7 @@ static int rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int
                          const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d, int64_t *seg_off_d,
                          uint64_t *pay0_out_d, uint64_t *pay1_out_d, int32_t *bad_d, void *workspace_d,
                          size_t workspace_bytes, void *stream, int32_t *sorted_keys_d = nullptr,
-                         const uint32_t *hist0_d = nullptr);
+                         const uint32_t *hist0_d = nullptr, int32_t *nflag_d = nullptr, int32_t narrow_mask = 0);
 
 extern "C" int fdx_rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys,
                                  const uint8_t *flag_d, const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d,
@@ -777,6 +934,31 @@ extern "C" int fdx_rekey_payload_hist0(const int32_t *keys_d, int64_t n, int32_t
                          reinterpret_cast<const uint32_t *>(hist0_d));
 }
 
+extern "C" int fdx_rekey_payload_narrow(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys,
+                                        const uint8_t *flag_d, const int64_t *ts_ns_d, const double *amount_d,
+                                        int32_t *perm_d, int64_t *seg_off_d, void *ts_out_d, void *amount_out_d,
+                                        int32_t *bad_d, const void *hist0_d, int32_t *narrow_flag_d,
+                                        int32_t narrow_mask, void *workspace_d, size_t workspace_bytes,
+                                        void *stream) {
+    FDX_REQUIRE(narrow_flag_d, "null narrow_flag_d");
+    FDX_REQUIRE(narrow_mask == 0 || narrow_mask == FDX_NARROW_TS || narrow_mask == (FDX_NARROW_TS | FDX_NARROW_AMOUNT),
+                "narrow_mask: 0, FDX_NARROW_TS or FDX_NARROW_TS | FDX_NARROW_AMOUNT");
+    FDX_REQUIRE(n == 0 || ts_ns_d, "the narrow re-key carries at least the timestamps");
+    FDX_REQUIRE(!(bad_d && hist0_d), "the id-range count is taken by fdx_rekey_hist0 when hist0_d is given");
+    return rekey_payload(keys_d, n, key_bits, n_keys, flag_d, reinterpret_cast<const uint64_t *>(ts_ns_d),
+                         reinterpret_cast<const uint64_t *>(amount_d), perm_d, seg_off_d,
+                         reinterpret_cast<uint64_t *>(ts_out_d), reinterpret_cast<uint64_t *>(amount_out_d), bad_d,
+                         workspace_d, workspace_bytes, stream, nullptr, reinterpret_cast<const uint32_t *>(hist0_d),
+                         narrow_flag_d, narrow_mask);
+}
+
+extern "C" int fdx_narrow_windows_ok(const int64_t *window_ns, int32_t n_windows, int64_t delay_ns) {
+    if (!window_ns || n_windows < 1 || delay_ns % kNsPerSec != 0) return 0;
+    for (int i = 0; i < n_windows; ++i)
+        if (window_ns[i] <= 0 || window_ns[i] % kNsPerSec != 0) return 0;
+    return 1;
+}
+
 extern "C" int fdx_segment_offsets_sorted(const int32_t *sorted_keys_d, int64_t n, int64_t n_keys, int64_t *seg_off_d,
                                           void *stream) {
     FDX_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX, "n out of range");
@@ -794,7 +976,8 @@ static int rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int
                          const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d, int64_t *seg_off_d,
                          uint64_t *pay0_out_d, uint64_t *pay1_out_d, int32_t *bad_d, void *workspace_d,
                          size_t workspace_bytes, void *stream, int32_t *sorted_keys_d,
-                         const uint32_t *hist0_d) {
+                         const uint32_t *hist0_d, int32_t *nflag_d, int32_t narrow_mask) {
+    const bool allow_narrow = (narrow_mask & 1) != 0;
     FDX_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX, "n out of range");
     FDX_REQUIRE(key_bits >= 1 && key_bits <= 31, "key_bits must be in [1, 31]");
     FDX_REQUIRE(n_keys >= 1 && n_keys <= (int64_t(1) << key_bits), "n_keys must be in [1, 2^key_bits]");
@@ -803,6 +986,9 @@ static int rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int
                 "payload inputs and outputs go together (stream 1 needs stream 0)");
     hipStream_t st = as_stream(stream);
     if (bad_d && !hist0_d) FDX_HIP(hipMemsetAsync(bad_d, 0, sizeof(int32_t), st));  // (hist0: counted there)
+    // the narrow flag: clear = the 4-byte forms hold (the first pass raises it); not allowed, or
+    // nothing to convert: raised from the start, and only the wide launches follow
+    if (nflag_d) FDX_HIP(hipMemsetAsync(nflag_d, allow_narrow && n > 0 ? 0 : 1, sizeof(int32_t), st));
     if (n == 0) {
         if (seg_off_d) FDX_HIP(hipMemsetAsync(seg_off_d, 0, sizeof(int64_t) * (n_keys + 1), st));
         return FDX_OK;
@@ -821,7 +1007,8 @@ static int rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int
     uint32_t *kout = reinterpret_cast<uint32_t *>(sorted_keys_d);
     int rc = radix_sort<uint32_t>(reinterpret_cast<const uint32_t *>(keys_d), n, key_bits, 0u, kout,
                                   reinterpret_cast<uint32_t *>(perm_d), w, st, &sorted, pw, flag_d, pin, pout,
-                                  (uint64_t)n_keys, hist0_d ? nullptr : bad_d, hist0_d);
+                                  (uint64_t)n_keys, hist0_d ? nullptr : bad_d, hist0_d,
+                                  allow_narrow ? nflag_d : nullptr, (narrow_mask & 2) != 0);
     if (rc) return rc;
     if (kout && sorted != kout) {  // (no radix pass: the input order is the sorted one)
         hipLaunchKernelGGL(k_copy_u32, dim3(stream_grid(n, 256)), dim3(256), 0, st, sorted, kout, n);

@@ -385,13 +385,28 @@ __global__ void __launch_bounds__(kPlanWaves * kWave) k_layout_plan_small(const 
 // GROUPED: ts / amount are already in grouped order (fdx_rekey_payload carried them through
 // the re-key): slot (t, l) reads ts[seg_off[s] + t] -- each segment a sequential stream --
 // instead of ts[cperm[...]], a random HBM line per 8-byte element.
+// NARROW (fdx_rekey_payload_narrow's outputs; nflag = its device flag, loaded once per block):
+// flag clear, ts is int32 seconds relative to tbase[0] and amount int32 cents, and every element
+// is widened where it is loaded (tbase[0] + s * 1e9 and (double)c / 100.0: the input's own bits)
+// -- the slots, the staged timestamps and the searches are then what they are from the 8-byte
+// columns; flag raised, the columns are the 8-byte ones.  A uniform branch around the loads.
+// NAMT = false: only ts has a narrow form, amount is the float64 column (FDX_NARROW_TS alone).
 constexpr int kStartLds = 1024;  // segment rows staged per wave for the start searches
-template <bool STARTS, bool GROUPED = false>
-__global__ void __launch_bounds__(256) k_interleave(
+constexpr int64_t kNsPerSec = 1000000000LL;
+// interleave_groups is the block's work; k_interleave (8-byte columns) and k_interleave_narrow are
+// its kernels.
+template <bool STARTS, bool GROUPED, bool NARROW, bool NAMT>
+__device__ __forceinline__ void interleave_groups(
     const int64_t *__restrict__ seg_off, const int32_t *__restrict__ sorder, const int32_t *__restrict__ cperm,
     const uint32_t *__restrict__ goff, int64_t n_seg, int32_t S, const int64_t *__restrict__ ts,
     const double *__restrict__ amount, int64_t *__restrict__ its, double *__restrict__ iamt,
-    int32_t *__restrict__ irow, WinArgs win, int32_t n_win, int32_t *__restrict__ starts, int64_t n_slots) {
+    int32_t *__restrict__ irow, const WinArgs &win, int32_t n_win, int32_t *__restrict__ starts, int64_t n_slots,
+    const int32_t *__restrict__ nflag, const int64_t *__restrict__ tbase) {
+    static_assert(!NARROW || (STARTS && GROUPED), "the narrow form is the grouped fill with starts");
+    const int32_t *tsn = reinterpret_cast<const int32_t *>(ts);
+    const int32_t *cents = reinterpret_cast<const int32_t *>(amount);
+    const bool nar = NARROW && *nflag == 0;  // (uniform)
+    const int64_t tb = NARROW ? tbase[0] : 0;
     __shared__ int64_t s_ts[STARTS ? 4 : 1][STARTS ? kStartLds : 1];
     const int64_t g = blockIdx.x;
     const int rows_per_iter = blockDim.x / S;
@@ -425,6 +440,7 @@ __global__ void __launch_bounds__(256) k_interleave(
             double vam[E];
             int32_t vr[E], xi[E];
             bool okv[E];
+            int64_t kk[E];
 #pragma unroll
             for (int j = 0; j < E; ++j) {
                 const int e = j * 256 + (int)threadIdx.x;
@@ -433,12 +449,30 @@ __global__ void __launch_bounds__(256) k_interleave(
                 const int r = e - ls * R;
                 const int64_t t = t0 + r;
                 const bool ok = valid && t < s_sl[ls];
-                const int64_t k = ok ? s_sb[ls] + t : 0;  // row 0 stands in (n >= 1 here)
-                vr[j] = cperm[k];
-                vts[j] = ts[k];
-                vam[j] = amount[k];
+                kk[j] = ok ? s_sb[ls] + t : 0;  // row 0 stands in (n >= 1 here)
+                vr[j] = cperm[kk[j]];
                 okv[j] = ok;
                 xi[j] = valid ? r * S + ls : e;  // (past TS: padding words, never read)
+            }
+            if (NARROW && nar) {
+                int32_t ns[E], nc[E];
+#pragma unroll
+                for (int j = 0; j < E; ++j) {
+                    ns[j] = tsn[kk[j]];
+                    if constexpr (NAMT) nc[j] = cents[kk[j]];
+                    else vam[j] = amount[kk[j]];
+                }
+#pragma unroll
+                for (int j = 0; j < E; ++j) {
+                    vts[j] = tb + (int64_t)ns[j] * kNsPerSec;
+                    if constexpr (NAMT) vam[j] = (double)nc[j] / 100.0;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < E; ++j) {
+                    vts[j] = ts[kk[j]];
+                    vam[j] = amount[kk[j]];
+                }
             }
 #pragma unroll
             for (int j = 0; j < E; ++j) {
@@ -511,6 +545,7 @@ __global__ void __launch_bounds__(256) k_interleave(
             const int64_t L = seg_off[sg + 1] - seg_off[sg];
             // row t's ts: the grouped input (contiguous) or, gathering form, the slots just written
             const int64_t *gts = GROUPED ? ts + seg_off[sg] : its + base + ls;
+            const int32_t *gts32 = tsn + seg_off[sg];  // (nar: the segment's seconds)
             const int64_t gstride = GROUPED ? 1 : S;
             const bool in_lds = L <= kStartLds;
             if (in_lds && L > 0) {  // (an empty segment: nothing to stage or search)
@@ -520,9 +555,18 @@ __global__ void __launch_bounds__(256) k_interleave(
                 // re-reads and re-stores the last row (the same value to the same word)
                 constexpr int UF = kStartLds / kWave;
                 int64_t v[UF];
+                if (NARROW && nar) {
+                    int32_t v32[UF];
 #pragma unroll
-                for (int j = 0; j < UF; ++j)
-                    v[j] = __builtin_nontemporal_load(gts + (int64_t)min(lane + j * kWave, (int32_t)L - 1) * gstride);
+                    for (int j = 0; j < UF; ++j)
+                        v32[j] = __builtin_nontemporal_load(gts32 + min(lane + j * kWave, (int32_t)L - 1));
+#pragma unroll
+                    for (int j = 0; j < UF; ++j) v[j] = tb + (int64_t)v32[j] * kNsPerSec;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < UF; ++j)
+                        v[j] = __builtin_nontemporal_load(gts + (int64_t)min(lane + j * kWave, (int32_t)L - 1) * gstride);
+                }
 #pragma unroll
                 for (int j = 0; j < UF; ++j) lts[min(lane + j * kWave, (int32_t)L - 1)] = v[j];
             }
@@ -555,6 +599,8 @@ __global__ void __launch_bounds__(256) k_interleave(
             };
             if (in_lds)
                 search([&](int64_t j) { return lts[j]; });
+            else if (NARROW && nar)
+                search([&](int64_t j) { return tb + (int64_t)__builtin_nontemporal_load(gts32 + j) * kNsPerSec; });
             else
                 search([&](int64_t j) { return __builtin_nontemporal_load(gts + j * gstride); });
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -562,6 +608,27 @@ __global__ void __launch_bounds__(256) k_interleave(
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
     }
+}
+
+template <bool STARTS, bool GROUPED = false>
+__global__ void __launch_bounds__(256) k_interleave(
+    const int64_t *__restrict__ seg_off, const int32_t *__restrict__ sorder, const int32_t *__restrict__ cperm,
+    const uint32_t *__restrict__ goff, int64_t n_seg, int32_t S, const int64_t *__restrict__ ts,
+    const double *__restrict__ amount, int64_t *__restrict__ its, double *__restrict__ iamt,
+    int32_t *__restrict__ irow, WinArgs win, int32_t n_win, int32_t *__restrict__ starts, int64_t n_slots) {
+    interleave_groups<STARTS, GROUPED, false, false>(seg_off, sorder, cperm, goff, n_seg, S, ts, amount, its, iamt, irow,
+                                                     win, n_win, starts, n_slots, nullptr, nullptr);
+}
+
+template <bool NAMT>
+__global__ void __launch_bounds__(256) k_interleave_narrow(
+    const int64_t *__restrict__ seg_off, const int32_t *__restrict__ sorder, const int32_t *__restrict__ cperm,
+    const uint32_t *__restrict__ goff, int64_t n_seg, int32_t S, const int64_t *__restrict__ ts,
+    const double *__restrict__ amount, int64_t *__restrict__ its, double *__restrict__ iamt,
+    int32_t *__restrict__ irow, WinArgs win, int32_t n_win, int32_t *__restrict__ starts, int64_t n_slots,
+    const int32_t *__restrict__ nflag, const int64_t *__restrict__ tbase) {
+    interleave_groups<true, true, true, NAMT>(seg_off, sorder, cperm, goff, n_seg, S, ts, amount, its, iamt, irow, win,
+                                              n_win, starts, n_slots, nflag, tbase);
 }
 
 // One wave per group; the wave streams its group's rows through an LDS ring (coalesced
@@ -1243,13 +1310,25 @@ __device__ __forceinline__ void term_emit(int32_t *nb_out, double *risk_out, int
 // (> 64 in LDS, > 2 LR - 1 long -- never the owner side, which has one run per source rank)
 // is counted directly, O(L) per row.  Only segments with len_lo < L <= len_hi are processed
 // (the short / long passes of terminal_launch).
-template <bool RUNS, int LR = kTermLdsRows>
-__global__ void __launch_bounds__(kTermBlock) k_terminal_g(
+// NARROW (fdx_rekey_payload_narrow's ts output; nflag = its device flag, loaded once per block):
+// flag clear, gts is int32 seconds relative to a base common to all rows, widened to s * 1e9
+// where it is loaded -- the kernel compares differences of timestamps only, so the base drops
+// out and every search decides as on the int64 column; flag raised, gts is that column.
+// (terminal_segments is the work; k_terminal_g and k_terminal_g_narrow are its kernels)
+template <bool RUNS, int LR, bool NARROW>
+__device__ __forceinline__ void terminal_segments(
     const int64_t *__restrict__ gts, const uint8_t *__restrict__ gfraud, const int32_t *__restrict__ rows,
-    const int64_t *__restrict__ seg_off, int64_t n_seg, int64_t n, int64_t delay, WinArgs win, int32_t n_win,
+    const int64_t *__restrict__ seg_off, int64_t n_seg, int64_t n, int64_t delay, const WinArgs &win, int32_t n_win,
     int32_t *__restrict__ nb_out, double *__restrict__ risk_out, int64_t *__restrict__ rec_out,
-    int32_t *__restrict__ scratch, int64_t len_lo, int64_t len_hi, int64_t compact_n) {
+    int32_t *__restrict__ scratch, int64_t len_lo, int64_t len_hi, int64_t compact_n,
+    const int32_t *__restrict__ nflag) {
     static_assert(LR % kWave == 0 && LR <= 32768, "the merge packs a staging index in 15 bits");
+    const bool nar = NARROW && *nflag == 0;  // (uniform)
+    const int32_t *gts32 = reinterpret_cast<const int32_t *>(gts);
+    auto ts_at = [&](int64_t q) -> int64_t {
+        return NARROW && nar ? (int64_t)__builtin_nontemporal_load(gts32 + q) * kNsPerSec
+                             : __builtin_nontemporal_load(gts + q);
+    };
     constexpr int kMaxRunsLong = 2 * LR - 1;  // a long segment's run list in the stage's ts words
     __shared__ int64_t s_ts[kTermWaves][LR];
     __shared__ int32_t s_f[kTermWaves][LR + 1];
@@ -1282,7 +1361,7 @@ __global__ void __launch_bounds__(kTermBlock) k_terminal_g(
             int f = 0;
             if (j < L) {
                 f = fraud_of(b + j);
-                if (in_lds) lts[j] = gts[b + j];
+                if (in_lds) lts[j] = NARROW && nar ? (int64_t)gts32[b + j] * kNsPerSec : gts[b + j];
             }
             const int inc = wave_incl_scan(f, lane) + carry;
             if (j < L) {
@@ -1301,7 +1380,7 @@ __global__ void __launch_bounds__(kTermBlock) k_terminal_g(
         // its latency even for LDS addresses -- the binary searches are chains of such loads)
         auto T_lds = [&](int64_t j) -> int64_t { return lts[j]; };
         auto F_lds = [&](int64_t j) -> int32_t { return lf[j]; };
-        auto T_glb = [&](int64_t j) -> int64_t { return __builtin_nontemporal_load(gts + b + j); };
+        auto T_glb = [&](int64_t j) -> int64_t { return ts_at(b + j); };
         auto F_glb = [&](int64_t j) -> int32_t { return j == 0 ? 0 : __builtin_nontemporal_load(scratch + b + j - 1); };
         int nruns = 1;
         int32_t *lr = in_lds ? s_runs[RUNS ? wv : 0] : reinterpret_cast<int32_t *>(lts);
@@ -1457,6 +1536,23 @@ __global__ void __launch_bounds__(kTermBlock) k_terminal_g(
     }
 }
 
+#define FDX_TERM_G_ARGS                                                                                       \
+    const int64_t *__restrict__ gts, const uint8_t *__restrict__ gfraud, const int32_t *__restrict__ rows,    \
+        const int64_t *__restrict__ seg_off, int64_t n_seg, int64_t n, int64_t delay, WinArgs win, int32_t n_win, \
+        int32_t *__restrict__ nb_out, double *__restrict__ risk_out, int64_t *__restrict__ rec_out,           \
+        int32_t *__restrict__ scratch, int64_t len_lo, int64_t len_hi, int64_t compact_n
+template <bool RUNS, int LR = kTermLdsRows>
+__global__ void __launch_bounds__(kTermBlock) k_terminal_g(FDX_TERM_G_ARGS) {
+    terminal_segments<RUNS, LR, false>(gts, gfraud, rows, seg_off, n_seg, n, delay, win, n_win, nb_out, risk_out,
+                                       rec_out, scratch, len_lo, len_hi, compact_n, nullptr);
+}
+template <int LR>
+__global__ void __launch_bounds__(kTermBlock) k_terminal_g_narrow(FDX_TERM_G_ARGS, const int32_t *__restrict__ nflag) {
+    terminal_segments<false, LR, true>(gts, gfraud, rows, seg_off, n_seg, n, delay, win, n_win, nb_out, risk_out,
+                                       rec_out, scratch, len_lo, len_hi, compact_n, nflag);
+}
+#undef FDX_TERM_G_ARGS
+
 // The short-segment pass of the single-run case (segments of 1..kTermShortRows rows, 99.95 % of
 // the rows at config 2), software-pipelined across a wave's segments: the next segment's
 // timestamps and rows words are loaded into registers while the current one is searched, and
@@ -1470,12 +1566,17 @@ __global__ void __launch_bounds__(kTermBlock) k_terminal_g(
 // (8 dependent reads) rather than chunks x (hi search, then the window searches inside [0, hi)).
 // Bounds over [0, i) equal those over [0, hi): ts is sorted and every ts in [hi, i) exceeds
 // t - delay >= each window's bound.  NW = 0: the runtime window count, one row at a time.
-template <int NW>
-__global__ void __launch_bounds__(kTermBlock) k_terminal_short(
+// NARROW, nflag: as k_terminal_g (int32 seconds widened where they are loaded).
+// (terminal_short_segments is the work; k_terminal_short and k_terminal_short_narrow are its kernels)
+template <int NW, bool NARROW>
+__device__ __forceinline__ void terminal_short_segments(
     const int64_t *__restrict__ gts, const uint8_t *__restrict__ gfraud, const int32_t *__restrict__ rows,
-    const int64_t *__restrict__ seg_off, int64_t n_seg, int64_t n, int64_t delay, WinArgs win, int32_t n_win,
-    int32_t *__restrict__ nb_out, double *__restrict__ risk_out, int64_t *__restrict__ rec_out, int64_t compact_n) {
+    const int64_t *__restrict__ seg_off, int64_t n_seg, int64_t n, int64_t delay, const WinArgs &win, int32_t n_win,
+    int32_t *__restrict__ nb_out, double *__restrict__ risk_out, int64_t *__restrict__ rec_out, int64_t compact_n,
+    const int32_t *__restrict__ nflag) {
     constexpr int LR = kTermShortRows, CH = LR / kWave;
+    const bool nar = NARROW && *nflag == 0;  // (uniform)
+    const int32_t *gts32 = reinterpret_cast<const int32_t *>(gts);
     __shared__ int64_t s_ts[kTermWaves][LR];
     __shared__ int32_t s_f[kTermWaves][LR + 1];
     __shared__ int32_t s_r[kTermWaves][LR];
@@ -1498,16 +1599,20 @@ __global__ void __launch_bounds__(kTermBlock) k_terminal_short(
         }
         return n_seg;
     };
-    int64_t pts[CH];
+    int64_t pts[CH];  // (nar: the seconds, widened when they are staged)
     int32_t prw[CH];
     uint32_t pfr[CH];
     auto load = [&](int64_t b, int64_t L) {
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             const int64_t j = imin64(c * kWave + lane, L - 1);  // clamped: no branch
-            pts[c] = gts[b + j];
+            if (!(NARROW && nar)) pts[c] = gts[b + j];
             prw[c] = rows ? rows[b + j] : (int32_t)(b + j);
             pfr[c] = gfraud ? gfraud[b + j] : 0u;
+        }
+        if (NARROW && nar) {
+#pragma unroll
+            for (int c = 0; c < CH; ++c) pts[c] = gts32[b + imin64(c * kWave + lane, L - 1)];
         }
     };
     int64_t cb = 0, cl = 0;
@@ -1523,7 +1628,7 @@ __global__ void __launch_bounds__(kTermBlock) k_terminal_short(
             const bool in = j < cl;
             const int f = in ? (gfraud ? (pfr[c] != 0) : (int)((uint32_t)prw[c] >> 31)) : 0;
             if (in) {
-                lts[j] = pts[c];
+                lts[j] = NARROW && nar ? pts[c] * kNsPerSec : pts[c];
                 lr[j] = prw[c] & 0x7FFFFFFF;
             }
             const int inc = wave_incl_scan(f, lane) + carry;
@@ -1622,6 +1727,23 @@ __global__ void __launch_bounds__(kTermBlock) k_terminal_short(
     }
 }
 
+#define FDX_TERM_S_ARGS                                                                                       \
+    const int64_t *__restrict__ gts, const uint8_t *__restrict__ gfraud, const int32_t *__restrict__ rows,    \
+        const int64_t *__restrict__ seg_off, int64_t n_seg, int64_t n, int64_t delay, WinArgs win, int32_t n_win, \
+        int32_t *__restrict__ nb_out, double *__restrict__ risk_out, int64_t *__restrict__ rec_out, int64_t compact_n
+template <int NW>
+__global__ void __launch_bounds__(kTermBlock) k_terminal_short(FDX_TERM_S_ARGS) {
+    terminal_short_segments<NW, false>(gts, gfraud, rows, seg_off, n_seg, n, delay, win, n_win, nb_out, risk_out, rec_out,
+                                       compact_n, nullptr);
+}
+template <int NW>
+__global__ void __launch_bounds__(kTermBlock) k_terminal_short_narrow(FDX_TERM_S_ARGS,
+                                                                      const int32_t *__restrict__ nflag) {
+    terminal_short_segments<NW, true>(gts, gfraud, rows, seg_off, n_seg, n, delay, win, n_win, nb_out, risk_out, rec_out,
+                                      compact_n, nflag);
+}
+#undef FDX_TERM_S_ARGS
+
 // X[r][0..2] = amount, weekend, night (rows already in output order)
 __global__ void __launch_bounds__(256) k_assemble_time(const double *__restrict__ amount,
                                                        const uint8_t *__restrict__ weekend,
@@ -1707,10 +1829,11 @@ extern "C" int fdx_customer_windows(const int64_t *ts_ns_d, const double *amount
 // Every terminal-window launch: the short-segment pass (<= kTermShortRows rows, small LDS
 // stage, more resident waves) then the long pass (the 1,024-row stage, global memory beyond);
 // each skips the other's segments.
+// nflag (runs == false): gts is fdx_rekey_payload_narrow's output, in the form the flag names.
 static void terminal_launch(bool runs, const int64_t *gts, const uint8_t *gfr, const int32_t *rows,
                             const int64_t *seg_off, int64_t n_seg, int64_t n, int64_t delay_ns, const WinArgs &wa,
                             int32_t n_windows, int32_t *nb_d, double *risk_d, int64_t *rec_d, int32_t *scratch,
-                            hipStream_t st, int64_t compact_n = 0) {
+                            hipStream_t st, int64_t compact_n = 0, const int32_t *nflag = nullptr) {
     const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n_seg, kTermWaves), 256 * 16);
     const int64_t lo = kTermShortRows, inf = INT64_MAX;
 #define FDX_TERM_LAUNCH(R, LRV, A, B)                                                                           \
@@ -1721,13 +1844,19 @@ static void terminal_launch(bool runs, const int64_t *gts, const uint8_t *gfr, c
         FDX_TERM_LAUNCH(true, kTermShortRows, 0, kTermShortRows);
         FDX_TERM_LAUNCH(true, kTermLdsRows, lo, inf);
     } else {
-        if (n_windows == 3)  // every search of a segment interleaved
+        if (nflag) {  // (n_windows == 3: terminal_grouped requires it)
+            hipLaunchKernelGGL(k_terminal_short_narrow<3>, dim3(grid), dim3(kTermBlock), 0, st, gts, gfr, rows, seg_off,
+                               n_seg, n, delay_ns, wa, n_windows, nb_d, risk_d, rec_d, compact_n, nflag);
+            hipLaunchKernelGGL(k_terminal_g_narrow<kTermLdsRows>, dim3(grid), dim3(kTermBlock), 0, st, gts, gfr, rows,
+                               seg_off, n_seg, n, delay_ns, wa, n_windows, nb_d, risk_d, rec_d, scratch, lo, inf,
+                               compact_n, nflag);
+        } else if (n_windows == 3)  // every search of a segment interleaved
             hipLaunchKernelGGL(k_terminal_short<3>, dim3(grid), dim3(kTermBlock), 0, st, gts, gfr, rows, seg_off,
                                n_seg, n, delay_ns, wa, n_windows, nb_d, risk_d, rec_d, compact_n);
         else
             hipLaunchKernelGGL(k_terminal_short<0>, dim3(grid), dim3(kTermBlock), 0, st, gts, gfr, rows, seg_off,
                                n_seg, n, delay_ns, wa, n_windows, nb_d, risk_d, rec_d, compact_n);
-        FDX_TERM_LAUNCH(false, kTermLdsRows, lo, inf);
+        if (!nflag) FDX_TERM_LAUNCH(false, kTermLdsRows, lo, inf);
     }
 #undef FDX_TERM_LAUNCH
 }
@@ -1764,7 +1893,8 @@ extern "C" int fdx_terminal_windows(const int64_t *ts_ns_d, const uint8_t *fraud
 static int terminal_grouped(const int64_t *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
                             const int64_t *seg_off_d, int64_t n_seg, int64_t n, int64_t delay_ns,
                             const int64_t *window_ns, int32_t n_windows, int32_t runs, int32_t *nb_d, double *risk_d,
-                            int64_t *rec_d, int32_t *scratch_d, void *stream, bool compact = false) {
+                            int64_t *rec_d, int32_t *scratch_d, void *stream, bool compact = false,
+                            const int32_t *nflag_d = nullptr) {
     WinArgs wa;
     int rc = check_windows(window_ns, n_windows, &wa);
     if (rc) return rc;
@@ -1776,8 +1906,14 @@ static int terminal_grouped(const int64_t *gts_d, const uint8_t *gfraud_d, const
     FDX_REQUIRE(rec_d || (nb_d && risk_d), "no output");
     FDX_REQUIRE(!compact || (rec_d && n_windows == 3 && ((uintptr_t)rec_d & 15) == 0),
                 "compact records: W = 3, a 16-byte aligned record array");
+    if (nflag_d) {
+        FDX_REQUIRE(!runs && compact && n_windows == 3, "narrow payloads: compact records of single-run segments");
+        FDX_REQUIRE(delay_ns % kNsPerSec == 0, "narrow payloads need a whole-second delay");
+        for (int i = 0; i < n_windows; ++i)
+            FDX_REQUIRE(window_ns[i] % kNsPerSec == 0, "narrow payloads need whole-second windows (window %d)", i);
+    }
     terminal_launch(runs != 0, gts_d, gfraud_d, rows_d, seg_off_d, n_seg, n, delay_ns, wa, n_windows, nb_d, risk_d,
-                    rec_d, scratch_d, as_stream(stream), compact ? n : 0);
+                    rec_d, scratch_d, as_stream(stream), compact ? n : 0, nflag_d);
     FDX_LAUNCHED("k_terminal_g");
     return FDX_OK;
 }
@@ -1797,6 +1933,16 @@ extern "C" int fdx_terminal_windows_grouped_compact(const int64_t *gts_d, const 
                                                     int32_t *scratch_d, void *stream) {
     return terminal_grouped(gts_d, gfraud_d, rows_d, seg_off_d, n_seg, n, delay_ns, window_ns, n_windows, runs,
                             nullptr, nullptr, rec_d, scratch_d, stream, true);
+}
+
+extern "C" int fdx_terminal_windows_grouped_narrow(const void *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
+                                                   const int64_t *seg_off_d, int64_t n_seg, int64_t n,
+                                                   int64_t delay_ns, const int64_t *window_ns, int32_t n_windows,
+                                                   int64_t *rec_d, int32_t *scratch_d,
+                                                   const int32_t *narrow_flag_d, void *stream) {
+    FDX_REQUIRE(narrow_flag_d, "null narrow_flag_d");
+    return terminal_grouped(reinterpret_cast<const int64_t *>(gts_d), gfraud_d, rows_d, seg_off_d, n_seg, n, delay_ns,
+                            window_ns, n_windows, 0, nullptr, nullptr, rec_d, scratch_d, stream, true, narrow_flag_d);
 }
 
 extern "C" int fdx_assemble_features(int64_t n, int32_t n_windows, const double *amount_d,
@@ -1928,7 +2074,9 @@ extern "C" int fdx_customer_layout_plan_async(const int64_t *seg_off_d, int64_t 
 static int customer_layout_fill(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d, const int64_t *ts_d,
                                 const double *amount_d, int32_t n_windows, const int32_t *sorder_d,
                                 const uint32_t *goff_d, int64_t n_slots, int64_t *its_d, double *iamt_d,
-                                int32_t *irow_d, hipStream_t st, const WinArgs *wa, int32_t *starts_d, bool grouped) {
+                                int32_t *irow_d, hipStream_t st, const WinArgs *wa, int32_t *starts_d, bool grouped,
+                                const int32_t *nflag_d = nullptr, const int64_t *tbase_d = nullptr,
+                                bool narrow_amount = true) {
     FDX_REQUIRE(n_seg >= 1 && n_windows >= 1 && n_windows <= 64 && n_slots >= 0, "bad argument");
     FDX_REQUIRE(seg_off_d && cperm_d && ts_d && amount_d && sorder_d && goff_d && its_d && iamt_d && irow_d,
                 "null pointer");
@@ -1938,10 +2086,20 @@ static int customer_layout_fill(const int64_t *seg_off_d, int64_t n_seg, const i
         hipLaunchKernelGGL((k_interleave<false, true>), dim3((unsigned)n_groups), dim3(256), 0, st, seg_off_d,
                            sorder_d, cperm_d, goff_d, n_seg, S, ts_d, amount_d, its_d, iamt_d, irow_d, WinArgs{},
                            n_windows, (int32_t *)nullptr, n_slots);
-    else if (starts_d && grouped)
-        hipLaunchKernelGGL((k_interleave<true, true>), dim3((unsigned)n_groups), dim3(256), 0, st, seg_off_d, sorder_d,
-                           cperm_d, goff_d, n_seg, S, ts_d, amount_d, its_d, iamt_d, irow_d, *wa, n_windows, starts_d,
-                           n_slots);
+    else if (starts_d && grouped) {
+        if (nflag_d && narrow_amount)  // (the kernel takes the form the flag names)
+            hipLaunchKernelGGL(k_interleave_narrow<true>, dim3((unsigned)n_groups), dim3(256), 0, st,
+                               seg_off_d, sorder_d, cperm_d, goff_d, n_seg, S, ts_d, amount_d, its_d, iamt_d, irow_d,
+                               *wa, n_windows, starts_d, n_slots, nflag_d, tbase_d);
+        else if (nflag_d)
+            hipLaunchKernelGGL(k_interleave_narrow<false>, dim3((unsigned)n_groups), dim3(256), 0, st,
+                               seg_off_d, sorder_d, cperm_d, goff_d, n_seg, S, ts_d, amount_d, its_d, iamt_d, irow_d,
+                               *wa, n_windows, starts_d, n_slots, nflag_d, tbase_d);
+        else
+            hipLaunchKernelGGL((k_interleave<true, true>), dim3((unsigned)n_groups), dim3(256), 0, st, seg_off_d,
+                               sorder_d, cperm_d, goff_d, n_seg, S, ts_d, amount_d, its_d, iamt_d, irow_d, *wa, n_windows,
+                               starts_d, n_slots);
+    }
     else if (starts_d)
         hipLaunchKernelGGL(k_interleave<true>, dim3((unsigned)n_groups), dim3(256), 0, st, seg_off_d, sorder_d,
                            cperm_d, goff_d, n_seg, S, ts_d, amount_d, its_d, iamt_d, irow_d, *wa, n_windows, starts_d,
@@ -1966,6 +2124,25 @@ extern "C" int fdx_customer_layout_fill_starts_grouped(const int64_t *seg_off_d,
     FDX_REQUIRE(starts_d, "null pointer");
     return customer_layout_fill(seg_off_d, n_seg, cperm_d, gts_d, gamount_d, n_windows, sorder_d, goff_d, n_slots,
                                 its_d, iamt_d, irow_d, as_stream(stream), &wa, starts_d, true);
+}
+
+extern "C" int fdx_customer_layout_fill_starts_grouped_narrow(
+    const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d, const void *gts_d, const void *gamount_d,
+    const int64_t *window_ns, int32_t n_windows, const int32_t *sorder_d, const uint32_t *goff_d, int64_t n_slots,
+    int64_t *its_d, double *iamt_d, int32_t *irow_d, int32_t *starts_d, const int32_t *narrow_flag_d,
+    int32_t narrow_mask, const int64_t *ts_base_d, void *stream) {
+    WinArgs wa;
+    int rc = check_windows(window_ns, n_windows, &wa);
+    if (rc) return rc;
+    FDX_REQUIRE(starts_d && narrow_flag_d && ts_base_d, "null pointer");
+    FDX_REQUIRE(narrow_mask == FDX_NARROW_TS || narrow_mask == (FDX_NARROW_TS | FDX_NARROW_AMOUNT),
+                "narrow_mask: the re-key's, FDX_NARROW_TS or FDX_NARROW_TS | FDX_NARROW_AMOUNT");
+    for (int i = 0; i < n_windows; ++i)
+        FDX_REQUIRE(window_ns[i] % kNsPerSec == 0, "narrow payloads need whole-second windows (window %d)", i);
+    return customer_layout_fill(seg_off_d, n_seg, cperm_d, reinterpret_cast<const int64_t *>(gts_d),
+                                reinterpret_cast<const double *>(gamount_d), n_windows, sorder_d, goff_d, n_slots,
+                                its_d, iamt_d, irow_d, as_stream(stream), &wa, starts_d, true, narrow_flag_d,
+                                ts_base_d, (narrow_mask & FDX_NARROW_AMOUNT) != 0);
 }
 
 // plan + fill in one call (the slot count must fit max_slots: FDX_E_WORKSPACE with *n_slots_h

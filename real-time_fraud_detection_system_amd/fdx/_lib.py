@@ -16,6 +16,7 @@ FDX_OK = 0
 FDX_E_UNSUPPORTED = -3
 FDX_FLAGS_NOTEBOOK = 0
 FDX_FLAGS_SPARK = 1
+FDX_NARROW_TS, FDX_NARROW_AMOUNT = 1, 2  # fdx_rekey_payload_narrow's narrow_mask
 FDX_ROWS_INPUT_ORDER = 1  # fdx_forest_prepare_grouped_rows: the featurized table by input row
 FDX_ROWS_SLOT_ORDER = 2   # ... by scoring slot (coalesced; each record carries its row)
 FDX_KEY_MOD, FDX_KEY_DIV, FDX_KEY_SUB = 0, 1, 2
@@ -110,6 +111,12 @@ SIGNATURES = {
     "fdx_rekey_hist0_size": (c_sz, [c_i64, c_i32]),
     "fdx_rekey_hist0": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, c_sz, P, P]),
     "fdx_rekey_payload_hist0": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, P, c_sz, P]),
+    "fdx_rekey_payload_narrow": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, P, P, c_i32, P, c_sz,
+                                                P]),
+    "fdx_narrow_windows_ok": (ctypes.c_int, [P, c_i32, c_i64]),
+    "fdx_customer_layout_fill_starts_grouped_narrow": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i32, P, P, c_i64, P, P,
+                                                                       P, P, P, c_i32, P, P]),
+    "fdx_terminal_windows_grouped_narrow": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i64, P, c_i32, P, P, P, P]),
     "fdx_terminal_windows_grouped": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i64, P, c_i32, c_i32, P, P, P, P, P]),
     "fdx_terminal_windows_grouped_compact": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i64, P, c_i32, c_i32, P, P,
                                                             P]),

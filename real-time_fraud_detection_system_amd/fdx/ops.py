@@ -124,7 +124,8 @@ def rekey(keys: torch.Tensor, n_keys: int, stream=None, want_sorted_keys: bool =
 
 def rekey_payload(keys: torch.Tensor, n_keys: int, pay0: torch.Tensor | None = None, pay1: torch.Tensor | None = None,
                   flag: torch.Tensor | None = None, stream=None, seg_off: bool = True, bad: torch.Tensor | None = None,
-                  alloc=None, keys_out: torch.Tensor | None = None, hist0: torch.Tensor | None = None):
+                  alloc=None, keys_out: torch.Tensor | None = None, hist0: torch.Tensor | None = None,
+                  narrow: bool | int | None = None):
     """rekey that also moves up to two 8-byte columns (int64 / float64, input row order) into
     grouped order inside the radix passes; flag (uint8 per row) is packed into bit 31 of perm.
     bad (int32 device scalar): receives the number of keys outside [0, n_keys), counted in the
@@ -136,7 +137,16 @@ def rekey_payload(keys: torch.Tensor, n_keys: int, pay0: torch.Tensor | None = N
     so bad must be None).
     -> (perm int32, seg_off int64[n_keys+1] (None with seg_off=False or keys_out), pay0 grouped |
     None, pay1 grouped | None).  alloc: see Arena (outputs "perm", "seg", "pay0", "pay1", scratch
-    "rekey_ws")."""
+    "rekey_ws").
+    narrow (not None): fdx_rekey_payload_narrow -- pay0 is the int64 timestamps, pay1 (optional) the
+    float64 amounts, and they travel as int32 seconds / int32 cents when every value has that form
+    exactly (decided on the device, no host sync).  A fifth output, a Narrow (the int32 [1] device
+    flag + the mask that was tried), says which form the grouped columns hold (flag 0: the 4-byte
+    forms in the first 4 n bytes of each column of the mask; else the 8-byte columns); hand it to
+    customer_layout_fill / terminal_windows_* as narrow=.  narrow=True: every column given;
+    _lib.FDX_NARROW_TS: the timestamps alone (pay1 stays 8 bytes, unchecked); False / 0 (the
+    caller's windows are not whole seconds, narrow_windows_ok): the same call with the flag raised
+    from the start -- the wide path alone."""
     _dev(keys, torch.int32, "keys")
     n = keys.numel()
     dev = keys.device
@@ -157,6 +167,23 @@ def rekey_payload(keys: torch.Tensor, n_keys: int, pay0: torch.Tensor | None = N
     L = _lib.load()
     ws = A("rekey_ws", max(L.fdx_rekey_payload_workspace_size(n, kb, (pay0 is not None) + (pay1 is not None)), 1),
            torch.uint8)
+    if narrow is not None:
+        if keys_out is not None or pay0 is None or pay0.dtype != torch.int64 or \
+                (pay1 is not None and pay1.dtype != torch.float64):
+            raise FdxError("narrow: pay0 = int64 timestamps, pay1 = float64 amounts or None, no keys_out")
+        if hist0 is not None and (bad is not None or hist0.numel() < L.fdx_rekey_hist0_size(n, kb)):
+            raise FdxError("hist0 takes no bad (counted by rekey_hist0) and must hold fdx_rekey_hist0_size bytes")
+        if bad is not None:
+            _dev(bad, torch.int32, "bad")
+        mask = (_lib.FDX_NARROW_TS | _lib.FDX_NARROW_AMOUNT) if narrow is True else int(narrow)
+        if pay1 is None:
+            mask &= _lib.FDX_NARROW_TS
+        nflag = A("nflag", 1, torch.int32)
+        check(L.fdx_rekey_payload_narrow(_ptr(keys), n, kb, int(n_keys), _ptr(flag), _ptr(pay0), _ptr(pay1), _ptr(perm),
+                                         _ptr(seg), _ptr(o0), _ptr(o1), _ptr(bad), _ptr(hist0), _ptr(nflag),
+                                         mask, _ptr(ws), ws.numel(), _s(stream)),
+              "fdx_rekey_payload_narrow")
+        return perm, seg, o0, o1, Narrow(nflag, mask)
     if hist0 is not None:
         if bad is not None or keys_out is not None:
             raise FdxError("hist0 takes neither bad (counted by rekey_hist0) nor keys_out")
@@ -183,6 +210,40 @@ def rekey_payload(keys: torch.Tensor, n_keys: int, pay0: torch.Tensor | None = N
         check(L.fdx_rekey_payload(_ptr(keys), n, kb, int(n_keys), _ptr(flag), _ptr(pay0), _ptr(pay1), _ptr(perm),
                                   _ptr(seg), _ptr(o0), _ptr(o1), _ptr(ws), ws.numel(), _s(stream)), "fdx_rekey_payload")
     return perm, seg, o0, o1
+
+
+def narrow_windows_ok(windows_ns: Sequence[int], delay_ns: int = 0) -> bool:
+    """Whether the narrow payload forms may be used with these windows and this delay (ns): all
+    whole seconds (fdx_narrow_windows_ok) -- rekey_payload(narrow=...) takes the answer."""
+    w = (ctypes.c_int64 * len(windows_ns))(*[int(x) for x in windows_ns])
+    return bool(_lib.load().fdx_narrow_windows_ok(w, len(windows_ns), int(delay_ns)))
+
+
+class Narrow:
+    """rekey_payload(narrow=...)'s fifth output: flag (device int32 [1]; 0 = the columns of mask
+    hold their 4-byte forms) and mask (_lib.FDX_NARROW_TS | FDX_NARROW_AMOUNT: what was tried)."""
+
+    def __init__(self, flag: torch.Tensor, mask: int):
+        self.flag, self.mask = flag, int(mask)
+
+    def holds(self) -> bool:
+        """Whether the narrow forms held (host-synchronising: for tests and tools)."""
+        return int(self.flag.item()) == 0
+
+
+def narrow_unpack(col: torch.Tensor, nar: Narrow, ts_base: torch.Tensor | None = None) -> torch.Tensor:
+    """A grouped column of rekey_payload(narrow=...) as its 8-byte values (host-synchronising: for
+    tests and tools).  int64 column: ts_base[0] + seconds * 1e9; float64: cents / 100.0."""
+    bit = _lib.FDX_NARROW_TS if col.dtype == torch.int64 else _lib.FDX_NARROW_AMOUNT
+    if not nar.holds() or not (nar.mask & bit):
+        return col
+    n = col.numel()
+    v = col.view(torch.int32)[:n]
+    if col.dtype == torch.int64:
+        return ts_base[0] + v.to(torch.int64) * 1_000_000_000
+    # (numpy's IEEE division, as the kernels divide: torch divides by a scalar as a multiplication by
+    # its reciprocal on the GPU, 1 ulp off for some cents)
+    return torch.from_numpy(v.cpu().numpy().astype(np.float64) / 100.0).to(col.device)
 
 
 def rekey_hist0(keys: torch.Tensor, n_keys: int, stream=None, bad: torch.Tensor | None = None, alloc=None):
@@ -550,8 +611,11 @@ def customer_layout_plan_async(seg_off, n_windows: int, stream=None, alloc=None)
 
 
 def customer_layout_fill(plan: LayoutPlan, seg_off, cperm, gts, gamt, windows_days, stream=None,
-                         alloc=None) -> CustomerLayout:
-    """The second half: slots and window starts of a plan from GROUPED ts / amount (alloc: see Arena)."""
+                         alloc=None, narrow: Narrow | None = None,
+                         ts_base: torch.Tensor | None = None) -> CustomerLayout:
+    """The second half: slots and window starts of a plan from GROUPED ts / amount (alloc: see Arena).
+    narrow: rekey_payload(narrow=...)'s fifth output -- gts / gamt hold the form it names; ts_base: that
+    re-key's pay0 (the input timestamps; row 0 is the base of the narrow seconds)."""
     _dev(seg_off, torch.int64, "seg_off"); _dev(cperm, torch.int32, "cperm")
     _dev(gts, torch.int64, "ts_ns"); _dev(gamt, torch.float64, "amount")
     W = plan.n_windows
@@ -566,7 +630,13 @@ def customer_layout_fill(plan: LayoutPlan, seg_off, cperm, gts, gamt, windows_da
     iamt = A("iamt", m, torch.float64)
     irow = A("irow", m, torch.int32)
     starts = A("starts", W * m, torch.int32)
-    if m:
+    if m and narrow is not None and narrow.mask:
+        _dev(ts_base, torch.int64, "ts_base")
+        check(_lib.load().fdx_customer_layout_fill_starts_grouped_narrow(
+            _ptr(seg_off), seg_off.numel() - 1, _ptr(cperm), _ptr(gts), _ptr(gamt), _win_ns(windows_days), W,
+            _ptr(plan.sorder), _ptr(plan.goff), m, _ptr(its), _ptr(iamt), _ptr(irow), _ptr(starts),
+            _ptr(narrow.flag), narrow.mask, _ptr(ts_base), _s(stream)), "fdx_customer_layout_fill_starts_grouped_narrow")
+    elif m:
         check(_lib.load().fdx_customer_layout_fill_starts_grouped(
             _ptr(seg_off), seg_off.numel() - 1, _ptr(cperm), _ptr(gts), _ptr(gamt), _win_ns(windows_days), W,
             _ptr(plan.sorder), _ptr(plan.goff), m, _ptr(its), _ptr(iamt), _ptr(irow), _ptr(starts), _s(stream)),
@@ -608,11 +678,12 @@ def customer_windows_interleaved(lay: CustomerLayout, seg_off, windows_days=(1, 
 
 
 def terminal_windows_compact(gts, seg_off, rows=None, gfraud=None, delay_days=7, windows_days=(1, 7, 30),
-                             runs: bool = False, stream=None, alloc=None):
+                             runs: bool = False, stream=None, alloc=None, narrow: Narrow | None = None):
     """terminal_windows_grouped's count records by row in the COMPACT format (3 windows): an
     int64 [5 n] array, row r's 16-byte record at words [2 r, 2 r + 2), the overflow area
     [2 n, 5 n) (fdx.h fdx_terminal_windows_grouped_compact).  compact_records_unpack turns it
-    into the [n, 3] records (alloc: see Arena)."""
+    into the [n, 3] records (alloc: see Arena).  narrow: rekey_payload(narrow=...)'s fifth output
+    -- gts holds the form it names (fdx_terminal_windows_grouped_narrow)."""
     _dev(gts, torch.int64, "gts"); _dev(seg_off, torch.int64, "seg_off")
     if rows is not None:
         _dev(rows, torch.int32, "rows")
@@ -626,6 +697,15 @@ def terminal_windows_compact(gts, seg_off, rows=None, gfraud=None, delay_days=7,
     A = alloc or _fresh(gts.device)
     rec = A("rec", max(5 * n, 2), torch.int64)  # 256-byte aligned
     scratch = A("scratch", max(n, 1), torch.int32)
+    if narrow is not None and narrow.mask:
+        if runs:
+            raise FdxError("narrow: single-run segments only")
+        check(_lib.load().fdx_terminal_windows_grouped_narrow(_ptr(gts), _ptr(gfraud), _ptr(rows), _ptr(seg_off),
+                                                              seg_off.numel() - 1, n, int(delay_days) * NS_PER_DAY,
+                                                              _win_ns(windows_days), 3, _ptr(rec), _ptr(scratch),
+                                                              _ptr(narrow.flag), _s(stream)),
+              "fdx_terminal_windows_grouped_narrow")
+        return rec
     check(_lib.load().fdx_terminal_windows_grouped_compact(_ptr(gts), _ptr(gfraud), _ptr(rows), _ptr(seg_off),
                                                            seg_off.numel() - 1, n, int(delay_days) * NS_PER_DAY,
                                                            _win_ns(windows_days), 3, int(bool(runs)), _ptr(rec),

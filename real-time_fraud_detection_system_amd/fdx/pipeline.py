@@ -68,6 +68,16 @@ class FraudPipeline:
     # 1: the row assembly with its 64-bit slot arithmetic (what it ran before it kept the loop's
     # bookkeeping in 32-bit scalars; tools/step_ab.py measures the two -- DESIGN §4)
     assembly_index64 = 0
+    # 1: run_fused's re-keys carry ts as int32 seconds whenever every timestamp has that form exactly
+    # (decided on the device inside the first radix pass, wide fallback otherwise:
+    # ops.rekey_payload(narrow=); W = 3 with compact records and the exact walk).  0: the 8-byte
+    # column, as before (tools/step_ab.py measures the two -- DESIGN §3)
+    narrow_payloads = 1
+    # 1: with narrow_payloads, the customer re-key also tries amount as int32 cents.  Off by default:
+    # the handbook generator's scenario-3 frauds are a cents amount x 5 in float64 (385.45000000000005),
+    # which has no exact cents form, so on such a table every step would pay the converting pass and
+    # then the wide passes (DESIGN §3 has the measurement)
+    narrow_amounts = 0
     # how long the host polls for the layout plan's slot count before a blocking wait: the plan of
     # step k lands only after step k - 1's forest (6.6 ms at configs[1]) when steps are queued back
     # to back, and a blocking hipEventSynchronize woke up ~150 us after it (profiles/r06t trace: plan
@@ -91,6 +101,9 @@ class FraudPipeline:
         self.n_features = 3 + 4 * len(self.windows_days)
         self._ws = None
         self._slots_hint = None
+        # run_fused: which form each re-key's columns took in the last step -- [customer, terminal],
+        # an ops.Narrow each (None: that re-key ran wide); for tests and tools
+        self.narrow_flags = [None, None]
 
     def featurize(self, ts_ns, customer, terminal, amount, fraud, n_customers: int, n_terminals: int,
                   assemble: bool = True, time_sort: bool = False, stream=None) -> Features:
@@ -211,6 +224,12 @@ class FraudPipeline:
                 # grouped order
                 scan = self.avg_mode == "scan"
                 walk = W >= 3  # the two-kernel walk serves >= 3 windows; fewer use the one-pass ring kernel
+                compact = self.compact_records and W == 3
+                # the narrow payload forms: the consumers that read them are the layout fill and the
+                # compact terminal windows (windows and delay are whole days: whole seconds)
+                narrow = None
+                if self.narrow_payloads and compact and walk and not scan:
+                    narrow = True if self.narrow_amounts else _lib.FDX_NARROW_TS
                 # the id range checks ride on the re-keys' first histogram pass (bad counts), read once
                 # everything is enqueued (out-of-range ids cannot make the re-keys write out of bounds)
                 bad = ar("bad", 2, torch.int32) if validate else None
@@ -223,10 +242,12 @@ class FraudPipeline:
                                               alloc=ar.scope("th0"))
                         if validate:  # (the count's copy here too, off the terminal chain)
                             rc_t = ops.KeyRangeCheck.from_count(bad[1:2], n_terminals, "terminal ids", side)
-                cperm, cseg, gts, gamt = ops.rekey_payload(customer, n_customers, ts_ns, amount, stream=main,
-                                                           bad=bad[0:1] if validate else None,
-                                                           alloc=ar.scope("cust", rk_shared))
+                cperm, cseg, gts, gamt, *cnf = ops.rekey_payload(customer, n_customers, ts_ns, amount, stream=main,
+                                                                 bad=bad[0:1] if validate else None,
+                                                                 alloc=ar.scope("cust", rk_shared), narrow=narrow)
                 mk("rekey_customer", main)
+                # (an ops.Narrow each, or None: which form that re-key's columns took; read by tests and tools)
+                self.narrow_flags = [cnf[0] if cnf else None, None]
                 if self.terminal_after_customer_rekey:
                     side.wait_stream(main)
                 # the walk's layout plan goes right behind the re-key; its slot count is read only
@@ -239,20 +260,21 @@ class FraudPipeline:
                 # perm); the records come out in input row order, read by the row assembly through irow.
                 # Allocated under the side stream's context, so that the caching allocator hands
                 # these buffers to nothing on the main stream while the side stream still uses them.
-                compact = self.compact_records and W == 3
                 with torch.cuda.stream(side):
                     mk("start", side)
-                    tperm, tseg, tgts, _ = ops.rekey_payload(terminal, n_terminals, ts_ns, flag=fraud, stream=side,
-                                                             bad=bad[1:2] if validate and th0 is None else None,
-                                                             alloc=ar.scope("term", rk_shared), hist0=th0)
+                    tperm, tseg, tgts, _, *tnf = ops.rekey_payload(terminal, n_terminals, ts_ns, flag=fraud, stream=side,
+                                                                   bad=bad[1:2] if validate and th0 is None else None,
+                                                                   alloc=ar.scope("term", rk_shared), hist0=th0,
+                                                                   narrow=narrow)
                     if validate:
                         rc.append(rc_t if th0 is not None else
                                   ops.KeyRangeCheck.from_count(bad[1:2], n_terminals, "terminal ids", side))
                     mk("rekey_terminal", side)
+                    self.narrow_flags[1] = tnf[0] if tnf else None
                     if compact:
                         trec = ops.terminal_windows_compact(tgts, tseg, rows=tperm, delay_days=self.delay_days,
                                                             windows_days=self.windows_days, stream=side,
-                                                            alloc=ar.scope("trec"))
+                                                            alloc=ar.scope("trec"), narrow=tnf[0] if tnf else None)
                     else:
                         trec = ops.terminal_windows_grouped(tgts, tseg, rows=tperm, delay_days=self.delay_days,
                                                             windows_days=self.windows_days, stream=side)
@@ -263,7 +285,8 @@ class FraudPipeline:
                     if pending is not None:
                         lay = ops.customer_layout_fill(pending.result(self.plan_spin_s), cseg, cperm, gts, gamt,
                                                        self.windows_days, main,
-                                                       alloc=ar.scope("lay"))
+                                                       alloc=ar.scope("lay"), narrow=cnf[0] if cnf else None,
+                                                       ts_base=ts_ns)
                     else:
                         lay = ops.customer_layout(cseg, cperm, gts, gamt, W, main, self._slots_hint,
                                                   self.windows_days if walk else None, grouped=True)
