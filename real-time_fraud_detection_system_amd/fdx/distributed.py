@@ -30,7 +30,7 @@ import torch.distributed as dist
 
 from . import _lib, ops
 from ._lib import check
-from .pipeline import check_rows_out
+from .pipeline import Features, _CustomerHalf, check_rows_out
 
 
 class GpuKernels:
@@ -233,6 +233,7 @@ class ShardedPipeline:
         self.customer_base = customer_base
         self.n_customers_local = n_customers_local
         self.group = group
+        self._side = None  # the exchange's stream, created on first use
 
     def _range(self, n_customers_local=None):
         n = self.n_customers_local if n_customers_local is None else int(n_customers_local)
@@ -250,24 +251,16 @@ class ShardedPipeline:
         base, n_local = self._range(n_customers_local)
         cust = ops.key_map(customer, _lib.FDX_KEY_SUB, base) if base else customer
         bad = torch.empty(1, dtype=torch.int32, device=ts.device)
-        cperm, cseg, gts, gamt = ops.rekey_payload(cust, n_local, ts, amount, bad=bad)
+        cperm, cseg, cnb, cavg = p.customer_features(cust, n_local, ts, amount, bad=bad)
         rc = ops.KeyRangeCheck.from_count(bad, n_local, "customer ids of this shard")
-        if p.avg_mode == "scan":
-            cnb, cavg = ops.customer_windows_scan(gts, gamt, cseg, p.windows_days)
-        else:
-            cnb, cavg = ops.customer_windows(gts, gamt, cseg, p.windows_days)
-        n = ts.numel()
-        ld = 16 if p.n_features <= 16 else p.n_features
-        X = torch.empty((n, ld), dtype=torch.float64, device=ts.device)
-        P = ops._ptr
-        check(_lib.load().fdx_assemble_features(n, W, P(amount), P(we), P(ni), P(cperm), P(cnb), P(cavg), None,
-                                                None, None, P(X), ld, ops._s()), "fdx_assemble_features")
+        # (the terminal columns are left to the reply: X is a view of the padded matrix, same rows)
+        X = p.assemble(Features(we, ni, cperm, cseg, cnb, cavg, None, None, None, None), amount)
         back, send_perm = exchange_terminal_features(GpuKernels, ts, terminal, fraud, self.world,
                                                      self.n_terminals_total, p.windows_days, p.delay_days,
                                                      self.group)
         GpuKernels.reply_assemble(back, send_perm, W, X, 3 + 2 * W)
         rc.check()
-        return X[:, : p.n_features]
+        return X
 
     def run(self, ts, customer, terminal, amount, fraud, proba, ws, events=None, n_customers_local: int | None = None,
             mark=None, stats=None, rows_out=None):
@@ -279,14 +272,13 @@ class ShardedPipeline:
         and bytes per peer of this step's exchange (exchange_finish)."""
         mk = mark or (lambda _name, _st: None)
         p = self.pipe
-        W = len(p.windows_days)
         check_rows_out(rows_out, ts)
         base, n_local = self._range(n_customers_local)
         # The terminal exchange (RCCL all-to-all there and back + the owner-side windows)
         # runs on a side stream, overlapped with the customer half on the main stream; the
         # two meet at the scoring-row assembly.
         main = torch.cuda.current_stream()
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=ts.device, priority=_SHARD_SIDE_PRIORITY)
         side = self._side
         mk("start", main)
@@ -296,21 +288,14 @@ class ShardedPipeline:
             state = exchange_begin(GpuKernels, terminal, self.world, self.group)
             mk("exchange_splits", side)
         cust = ops.key_map(customer, _lib.FDX_KEY_SUB, base) if base else customer
-        # the customer half's intermediates in the pipeline's arena (as FraudPipeline.run_fused; they
+        # the customer half as FraudPipeline.run_fused's (its buffers under names of this step's own; they
         # are used on this stream only, so stream order is the reuse order)
-        if getattr(p, "_arena", None) is None or p._arena.device != ts.device:
-            p._arena = ops.Arena(ts.device)
-        ar = p._arena if p.use_arena else None
-        A = (lambda name: ar.scope("sh." + name)) if ar is not None else (lambda name: None)
+        half = _CustomerHalf(p, ts.device, main, mk, prefix="sh.")
         bad = torch.empty(1, dtype=torch.int32, device=ts.device)  # counted in the re-key's first pass
-        cperm, cseg, gts, gamt = ops.rekey_payload(cust, n_local, ts, amount, bad=bad, alloc=A("cust"))
-        rc = ops.KeyRangeCheck.from_count(bad, n_local, "customer ids of this shard")  # read after the layout's sync
-        mk("rekey_customer", main)
-        scan = p.avg_mode == "scan"
-        walk = W >= 3
+        half.rekey(cust, n_local, ts, amount, bad, "customer ids of this shard")
         # the walk's layout plan right behind the re-key (no host wait): it runs while the host
         # waits for the exchange's split sizes below
-        pending = ops.customer_layout_plan_async(cseg, W, alloc=A("plan")) if (walk and not scan) else None
+        half.plan()
         # the exchange's split-size sync waits only for the (short) owner re-key on the side
         # stream; enqueueing the whole exchange before the layout's host sync keeps the side
         # stream busy while the customer re-key runs
@@ -319,29 +304,16 @@ class ShardedPipeline:
                                               self.n_terminals_total, p.windows_days, p.delay_days, self.group,
                                               mark=lambda name: mk(name, side), stats=stats)
             sinv = ops.invert_perm(send_perm)   # local row -> send position (= reply record)
-        if pending is not None:
-            lay = ops.customer_layout_fill(pending.result(p.plan_spin_s), cseg, cperm, gts, gamt, p.windows_days,
-                                           alloc=A("lay"))
-        else:
-            lay = ops.customer_layout(cseg, cperm, gts, gamt, W, None, p._slots_hint,
-                                      p.windows_days if walk else None, grouped=True)  # (host sync on main)
-        mk("customer_layout", main)
-        rc.check()
-        p._slots_hint = lay.its.numel()
-        p.last_slots = lay.n_slots  # (the FeatureTable's slots, as FraudPipeline.run_fused)
-        if scan:
-            inb, isum = ops.customer_windows_scan(gts, gamt, cseg, p.windows_days, lay=lay)
-        elif walk:
-            inb, isum = ops.customer_windows_walk(lay, cseg, alloc=A("walk"))
-        else:
-            inb, isum = ops.customer_windows_interleaved(lay, cseg, p.windows_days)
-        mk("customer_walk", main)
+        lay, inb, isum = half.windows()  # (host sync on main: the layout's slot count)
+        for c in half.checks:
+            c.check()
         main.wait_stream(side)
         back.record_stream(main)
         sinv.record_stream(main)
         ws = p._forest_ws(lay.n_slots, ws, ts.device)
         ops.forest_prepare_grouped(p.forest, p.flags_mode, lay.its, lay.iamt, inb, isum, lay.irow, sinv, back, ws,
-                                   n=lay.n_slots, val_is_sum=True, rows_out=rows_out)
+                                   n=lay.n_slots, val_is_sum=True, rows_out=rows_out,
+                                   index64=bool(p.assembly_index64))
         mk("assemble_rows", main)
         if events is not None:
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

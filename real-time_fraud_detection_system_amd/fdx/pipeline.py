@@ -54,17 +54,6 @@ class FraudPipeline:
     # 3.58-3.60 ms (and at high priority); profiles/r05ak_stream_order_ab.txt, r05an_priority_ab.txt.
     crit_priority = 0
     side_priority = -1
-    terminal_after_customer_rekey = True
-    # the terminal re-key's first histogram pass (+ scan, + the terminal id-range count) runs on
-    # the side stream at the step's start, beside the customer re-key, instead of after it on the
-    # critical chain (fdx_rekey_hist0 / fdx_rekey_payload_hist0)
-    terminal_hist_ahead = 1
-    # the assembly and the forest on the terminal half's stream (the half that ends last), the NaN
-    # flag cleared on the main stream beforehand (tools/step_ab.py measures it against 0)
-    tail_on_side = 1
-    # the step's intermediates in the pipeline's own arena (ops.Arena; 0: torch's caching allocator
-    # per call, as before round 6 -- tools/step_ab.py measures the two)
-    use_arena = 1
     # 1: the row assembly with its 64-bit slot arithmetic (what it ran before it kept the loop's
     # bookkeeping in 32-bit scalars; tools/step_ab.py measures the two -- DESIGN §4)
     assembly_index64 = 0
@@ -100,7 +89,10 @@ class FraudPipeline:
         self.forest = forest
         self.n_features = 3 + 4 * len(self.windows_days)
         self._ws = None
-        self._slots_hint = None
+        # the scoring step's own: two streams (run_fused) and the arena, created on first use on a
+        # device; the last layout's buffer size (the next one-shot layout's first try) and slot count
+        self._side = self._crit = self._arena = None
+        self._slots_hint = self.last_slots = None
         # run_fused: which form each re-key's columns took in the last step -- [customer, terminal],
         # an ops.Narrow each (None: that re-key ran wide); for tests and tools
         self.narrow_flags = [None, None]
@@ -121,12 +113,7 @@ class FraudPipeline:
             return f
         n = ts_ns.numel()
         we, ni = ops.time_flags(ts_ns, self.flags_mode, stream)
-        # the re-keys carry the columns the window kernels read (grouped, sequential)
-        cperm, cseg, gts, gamt = ops.rekey_payload(customer, n_customers, ts_ns, amount, stream=stream)
-        if self.avg_mode == "scan":
-            cnb, cavg = ops.customer_windows_scan(gts, gamt, cseg, self.windows_days, stream=stream)
-        else:
-            cnb, cavg = ops.customer_windows(gts, gamt, cseg, self.windows_days, stream)
+        cperm, cseg, cnb, cavg = self.customer_features(customer, n_customers, ts_ns, amount, stream)
         tperm, tseg, tgts, _ = ops.rekey_payload(terminal, n_terminals, ts_ns, stream=stream)
         tnb, trisk = ops.terminal_windows_grouped(tgts, tseg, gfraud=ops.gather(fraud, tperm, stream),
                                                   delay_days=self.delay_days, windows_days=self.windows_days,
@@ -136,7 +123,19 @@ class FraudPipeline:
             f.X = self.assemble(f, amount, stream)
         return f
 
+    def customer_features(self, customer, n_customers: int, ts_ns, amount, stream=None, bad=None):
+        """featurize's customer part -> (cust_perm, cust_seg, cust_nb, cust_avg): the re-key carries
+        the columns the window kernels read (grouped, sequential); bad: ops.rekey_payload's count of
+        ids outside [0, n_customers)."""
+        cperm, cseg, gts, gamt = ops.rekey_payload(customer, n_customers, ts_ns, amount, stream=stream, bad=bad)
+        if self.avg_mode == "scan":
+            cnb, cavg = ops.customer_windows_scan(gts, gamt, cseg, self.windows_days, stream=stream)
+        else:
+            cnb, cavg = ops.customer_windows(gts, gamt, cseg, self.windows_days, stream)
+        return cperm, cseg, cnb, cavg
+
     def assemble(self, f: Features, amount: torch.Tensor, stream=None) -> torch.Tensor:
+        """f's terminal fields None: those columns are left for the caller to fill."""
         n = amount.numel()
         ld = 16 if self.n_features <= 16 else self.n_features
         X = torch.empty((n, ld), dtype=torch.float64, device=amount.device)
@@ -172,8 +171,8 @@ class FraudPipeline:
         input row order.
 
         Streams: the terminal half (re-key + windows) runs on a side stream, concurrently with
-        the customer half's layout plan, layout and walk (it waits for the customer re-key:
-        terminal_after_customer_rekey) -- the customer walk is a latency-bound recurrence with one
+        the customer half's layout plan, layout and walk (it waits for the customer re-key; only its
+        first histogram pass runs beside that) -- the customer walk is a latency-bound recurrence with one
         lane per (customer, window) that leaves most SIMDs idle; the two meet at the row assembly.  The
         customer half, assembly and forest run on a stream of the pipeline's own, the terminal half
         on a higher-priority one (crit_priority / side_priority), ordered after the caller's stream
@@ -194,20 +193,15 @@ class FraudPipeline:
         check_rows_out(rows_out, ts_ns)
         if ts_ns.numel() == 0:  # an empty table: nothing to score
             return proba
-        if getattr(self, "_side", None) is None or self._side.device != ts_ns.device:
+        if self._side is None or self._side.device != ts_ns.device:
             self._side = torch.cuda.Stream(device=ts_ns.device, priority=self.side_priority)
             # two streams of the pipeline's own; their priorities: crit_priority / side_priority
             self._crit = torch.cuda.Stream(device=ts_ns.device, priority=self.crit_priority)
         main = self._crit if overlap else caller
         side = self._side if overlap else caller
-        # the step's intermediates live in an arena of the pipeline's own (ops.Arena): a repeated
-        # step allocates nothing; its buffers are reused by the next step, which the joins below
-        # order after every use (main waits for the caller and for the side stream's last step)
-        if getattr(self, "_arena", None) is None or self._arena.device != ts_ns.device:
-            self._arena = ops.Arena(ts_ns.device)
-        ar = self._arena if self.use_arena else _NoArena(ts_ns.device)
-        # the two re-keys' scratch is one buffer when the terminal re-key starts after the customer one
-        rk_shared = ("rekey_ws",) if self.terminal_after_customer_rekey else ()
+        # the customer half (its re-key shares its scratch with the terminal one, which starts after it)
+        half = _CustomerHalf(self, ts_ns.device, main, mk, shared=("rekey_ws",))
+        ar = half.arena
         if main is not caller:
             main.wait_stream(caller)
             main.wait_stream(side)
@@ -220,42 +214,35 @@ class FraudPipeline:
             with torch.cuda.stream(main):
                 mk("start", main)
                 side.wait_stream(main)
-                # customer half first (the critical path): the re-key carries ts and amount into
-                # grouped order
-                scan = self.avg_mode == "scan"
-                walk = W >= 3  # the two-kernel walk serves >= 3 windows; fewer use the one-pass ring kernel
                 compact = self.compact_records and W == 3
                 # the narrow payload forms: the consumers that read them are the layout fill and the
                 # compact terminal windows (windows and delay are whole days: whole seconds)
                 narrow = None
-                if self.narrow_payloads and compact and walk and not scan:
+                if self.narrow_payloads and compact and half.walk and not half.scan:
                     narrow = True if self.narrow_amounts else _lib.FDX_NARROW_TS
                 # the id range checks ride on the re-keys' first histogram pass (bad counts), read once
                 # everything is enqueued (out-of-range ids cannot make the re-keys write out of bounds)
                 bad = ar("bad", 2, torch.int32) if validate else None
                 th0 = None
+                # the terminal re-key's first histogram pass (+ scan, + the terminal id-range count) on
+                # the side stream at the step's start, beside the customer re-key, instead of after it
+                # on the critical chain (fdx_rekey_hist0 / fdx_rekey_payload_hist0)
                 # (overlapped mode only: on one stream it would just run first, and the per-stage
                 # times bench.py takes in that mode would book it to the customer re-key)
-                if self.terminal_hist_ahead and self.terminal_after_customer_rekey and main is not caller:
+                if overlap:
                     with torch.cuda.stream(side):
                         th0 = ops.rekey_hist0(terminal, n_terminals, side, bad=bad[1:2] if validate else None,
                                               alloc=ar.scope("th0"))
                         if validate:  # (the count's copy here too, off the terminal chain)
                             rc_t = ops.KeyRangeCheck.from_count(bad[1:2], n_terminals, "terminal ids", side)
-                cperm, cseg, gts, gamt, *cnf = ops.rekey_payload(customer, n_customers, ts_ns, amount, stream=main,
-                                                                 bad=bad[0:1] if validate else None,
-                                                                 alloc=ar.scope("cust", rk_shared), narrow=narrow)
-                mk("rekey_customer", main)
+                # customer half first (the critical path)
+                half.rekey(customer, n_customers, ts_ns, amount, bad[0:1] if validate else None, narrow=narrow)
                 # (an ops.Narrow each, or None: which form that re-key's columns took; read by tests and tools)
-                self.narrow_flags = [cnf[0] if cnf else None, None]
-                if self.terminal_after_customer_rekey:
-                    side.wait_stream(main)
+                self.narrow_flags = [half.nflag, None]
+                side.wait_stream(main)  # the terminal half waits for the re-key, not for the plan
                 # the walk's layout plan goes right behind the re-key; its slot count is read only
                 # after the terminal half is enqueued (no host wait between the two)
-                pending = ops.customer_layout_plan_async(cseg, W, main, alloc=ar.scope("plan")) \
-                    if (walk and not scan) else None
-                if validate:  # (its pinned copy behind the plan, not in front of it: up to 38 us)
-                    rc = [ops.KeyRangeCheck.from_count(bad[0:1], n_customers, "customer ids", main)]
+                half.plan()
                 # terminal half (side stream): the re-key carries ts (and TX_FRAUD in bit 31 of the
                 # perm); the records come out in input row order, read by the row assembly through irow.
                 # Allocated under the side stream's context, so that the caching allocator hands
@@ -264,11 +251,11 @@ class FraudPipeline:
                     mk("start", side)
                     tperm, tseg, tgts, _, *tnf = ops.rekey_payload(terminal, n_terminals, ts_ns, flag=fraud, stream=side,
                                                                    bad=bad[1:2] if validate and th0 is None else None,
-                                                                   alloc=ar.scope("term", rk_shared), hist0=th0,
+                                                                   alloc=ar.scope("term", ("rekey_ws",)), hist0=th0,
                                                                    narrow=narrow)
                     if validate:
-                        rc.append(rc_t if th0 is not None else
-                                  ops.KeyRangeCheck.from_count(bad[1:2], n_terminals, "terminal ids", side))
+                        half.checks.append(rc_t if th0 is not None else
+                                           ops.KeyRangeCheck.from_count(bad[1:2], n_terminals, "terminal ids", side))
                     mk("rekey_terminal", side)
                     self.narrow_flags[1] = tnf[0] if tnf else None
                     if compact:
@@ -281,56 +268,28 @@ class FraudPipeline:
                     mk("terminal_windows", side)
                 for t in (ts_ns, customer, terminal, fraud) + ((bad,) if validate else ()):
                     t.record_stream(side)  # inputs in use on the side stream
-                try:
-                    if pending is not None:
-                        lay = ops.customer_layout_fill(pending.result(self.plan_spin_s), cseg, cperm, gts, gamt,
-                                                       self.windows_days, main,
-                                                       alloc=ar.scope("lay"), narrow=cnf[0] if cnf else None,
-                                                       ts_base=ts_ns)
-                    else:
-                        lay = ops.customer_layout(cseg, cperm, gts, gamt, W, main, self._slots_hint,
-                                                  self.windows_days if walk else None, grouped=True)
-                except _lib.FdxError:
-                    if validate:  # ids outside the range are the likelier cause: report them
-                        for c in rc:
-                            c.check()
-                    raise
-                mk("customer_layout", main)
-                self._slots_hint = lay.its.numel()
-                self.last_slots = lay.n_slots
-                if scan:  # the windows straight from the grouped rows into the layout's slots
-                    inb, isum = ops.customer_windows_scan(gts, gamt, cseg, self.windows_days, lay=lay, stream=main)
-                elif walk:
-                    inb, isum = ops.customer_windows_walk(lay, cseg, main, alloc=ar.scope("walk"))
-                else:
-                    inb, isum = ops.customer_windows_interleaved(lay, cseg, self.windows_days, main)
-                mk("customer_walk", main)
+                lay, inb, isum = half.windows()
                 ws = self._forest_ws(lay.n_slots, ws, amount.device)
                 # the assembly and the forest run on the stream that finishes its half LAST -- the
                 # terminal half since round 5's reorder (it ends ~0.3 ms after the walk,
                 # profiles/r05br_step_timeline.txt) -- so that no cross-stream wait (~20 us) sits
                 # on the critical path; the workspace's NaN flag is cleared here, off it (5 us)
-                tail = side if overlap and self.tail_on_side else main
-                if tail is not main:
+                if overlap:
                     ops.forest_clear_flag(self.forest, lay.n_slots, ws, main)
-                    tail.wait_stream(main)
+                    side.wait_stream(main)
                     for t in (lay.its, lay.iamt, lay.irow, inb, isum, ws, proba, amount) + \
                             ((rows_out.buf,) if rows_out is not None else ()):
-                        t.record_stream(tail)
-                else:
-                    main.wait_stream(side)
-                    trec.record_stream(main)
-                with torch.cuda.stream(tail):
+                        t.record_stream(side)
+                with torch.cuda.stream(side):
                     ops.forest_prepare_grouped(self.forest, self.flags_mode, lay.its, lay.iamt, inb, isum, lay.irow,
-                                               None, trec, ws, tail, n=lay.n_slots, val_is_sum=True,
-                                               term_compact=compact, rows_out=rows_out, flag_cleared=tail is not main,
+                                               None, trec, ws, side, n=lay.n_slots, val_is_sum=True,
+                                               term_compact=compact, rows_out=rows_out, flag_cleared=overlap,
                                                index64=bool(self.assembly_index64))
-                    mk("assemble_rows", tail)
-                    ops.forest_traverse_perm(self.forest, lay.n_slots, ws, proba, lay.irow, tail)
-                    mk("forest_traverse", tail)
-                if validate:  # read once everything is enqueued (the counts ran in the re-keys)
-                    for c in rc:
-                        c.check()
+                    mk("assemble_rows", side)
+                    ops.forest_traverse_perm(self.forest, lay.n_slots, ws, proba, lay.irow, side)
+                    mk("forest_traverse", side)
+                for c in half.checks:  # read once everything is enqueued (the counts ran in the re-keys)
+                    c.check()
         finally:
             if main is not caller:
                 main.wait_stream(side)
@@ -346,17 +305,67 @@ class FraudPipeline:
         return self._ws
 
 
-class _NoArena:
-    """use_arena = 0: every alloc() a fresh tensor from torch's caching allocator."""
+class _CustomerHalf:
+    """The customer half of one scoring step, FraudPipeline.run_fused's and ShardedPipeline.run's
+    alike: rekey(), plan(), windows() enqueue on `stream` in that order, and between them the caller
+    enqueues its other half (the terminal re-key and windows, or the exchange).  The intermediates
+    live in an arena of the pipeline's own (ops.Arena): a repeated step allocates nothing; its
+    buffers are reused by the next step, which the caller's stream joins order after every use.
+    Buffer names: `prefix` + cust / plan / lay / walk (`shared`: see ops.Arena.scope).
+    checks: the step's pending id-range checks (the caller may append its own and reads them once
+    everything is enqueued)."""
 
-    def __init__(self, device):
-        self.device = device
+    def __init__(self, pipe: FraudPipeline, device, stream, mark, prefix: str = "", shared=()):
+        if pipe._arena is None or pipe._arena.device != device:
+            pipe._arena = ops.Arena(device)
+        self.pipe, self.arena, self.stream, self.mark, self.checks = pipe, pipe._arena, stream, mark, []
+        self.scope = lambda name: pipe._arena.scope(prefix + name, shared)
+        self.scan = pipe.avg_mode == "scan"
+        # the two-kernel walk serves >= 3 windows; fewer use the one-pass ring kernel
+        self.walk = len(pipe.windows_days) >= 3
 
-    def __call__(self, _name, numel, dtype):
-        return torch.empty(max(int(numel), 1), dtype=dtype, device=self.device)[:int(numel)]
+    def rekey(self, customer, n_customers: int, ts_ns, amount, bad=None, what: str = "customer ids", narrow=None):
+        """The re-key carries ts and amount into grouped order (narrow: ops.rekey_payload's); bad
+        (int32 [1] on the device, or None): its count of ids outside [0, n_customers)."""
+        self.ts_ns, self.bad = ts_ns, (bad, n_customers, what)
+        self.cperm, self.cseg, self.gts, self.gamt, *nf = ops.rekey_payload(
+            customer, n_customers, ts_ns, amount, stream=self.stream, bad=bad, alloc=self.scope("cust"), narrow=narrow)
+        self.mark("rekey_customer", self.stream)
+        self.nflag = nf[0] if nf else None
 
-    def scope(self, _prefix, _shared=()):
-        return None  # (the ops allocate fresh tensors themselves)
+    def plan(self):
+        """The walk's layout plan, enqueued without a host wait (windows() reads its slot count)."""
+        self.pending = ops.customer_layout_plan_async(self.cseg, len(self.pipe.windows_days), self.stream,
+                                                      alloc=self.scope("plan")) if self.walk and not self.scan else None
+        if self.bad[0] is not None:  # (its pinned copy behind the plan, not in front of it: up to 38 us)
+            self.checks.append(ops.KeyRangeCheck.from_count(*self.bad, self.stream))
+
+    def windows(self):
+        """Layout (host-synchronising: the slot count) and windows -> (lay, nb, rolling sum), by slot."""
+        p, st, cseg, gts, gamt = self.pipe, self.stream, self.cseg, self.gts, self.gamt
+        try:
+            if self.pending is not None:
+                lay = ops.customer_layout_fill(self.pending.result(p.plan_spin_s), cseg, self.cperm, gts, gamt,
+                                               p.windows_days, st, alloc=self.scope("lay"), narrow=self.nflag,
+                                               ts_base=self.ts_ns)
+            else:
+                lay = ops.customer_layout(cseg, self.cperm, gts, gamt, len(p.windows_days), st, p._slots_hint,
+                                          p.windows_days if self.walk else None, grouped=True)
+        except _lib.FdxError:
+            for c in self.checks:  # ids outside the range are the likelier cause: report them
+                c.check()
+            raise
+        self.mark("customer_layout", st)
+        p._slots_hint = lay.its.numel()
+        p.last_slots = lay.n_slots
+        if self.scan:  # the windows straight from the grouped rows into the layout's slots
+            inb, isum = ops.customer_windows_scan(gts, gamt, cseg, p.windows_days, lay=lay, stream=st)
+        elif self.walk:
+            inb, isum = ops.customer_windows_walk(lay, cseg, st, alloc=self.scope("walk"))
+        else:
+            inb, isum = ops.customer_windows_interleaved(lay, cseg, p.windows_days, st)
+        self.mark("customer_walk", st)
+        return lay, inb, isum
 
 
 def check_rows_out(rows_out, ts_ns: torch.Tensor) -> None:

@@ -1,7 +1,7 @@
 """A/B of FraudPipeline class switches on one box, alternating (tools only): the bench's step
 (configs[1], run_fused with the featurized table) timed as --steps steps per round, the settings
 alternating for --rounds rounds; prints the per-round ms/step of each setting and their medians.
-    python tools/step_ab.py tail_on_side=1 tail_on_side=0 [--rounds 6 --steps 10]
+    python tools/step_ab.py narrow_payloads=1 narrow_payloads=0 [--rounds 6 --steps 10]
 A setting is attr=value on FraudPipeline (ints)."""
 import argparse
 import json
