@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define FDX_ABI_VERSION 2
+#define FDX_ABI_VERSION 3
 
 #define FDX_OK 0
 #define FDX_E_INVALID (-1)     /* bad argument (null pointer, size, unsupported shape) */
@@ -78,29 +78,29 @@ int fdx_customer_windows(const int64_t *ts_ns_d, const double *amount_d, const i
  * time-ordered ts/amount through cperm_d (fdx_rekey output), writes the slot count to
  * *n_slots_h (host; this call synchronises the stream once) and fails with
  * FDX_E_WORKSPACE if it exceeds max_slots (it is at most n + (S-1)*max segment length).
- * goff_d needs n_groups+1 = ceil(n_seg/S)+1 entries. */
+ * goff_d needs n_groups+1 = ceil(n_seg/S)+1 entries.
+ *   window_ns + starts_d (both or neither, else FDX_E_INVALID): also every row's window starts
+ * (pandas' variable-window start: the first row j of the segment with ts_j > ts_t - window_ns[w],
+ * closed='right'), computed in the same kernel from the freshly gathered timestamps,
+ * segment-contiguous: row t of segment l of group g at starts_d[w * n_slots + goff_d[g] + l * Lg
+ * + t] (Lg = the group's longest segment; starts_d: room for n_windows * max_slots int32).
+ * Follow with fdx_customer_windows_walk; without them the layout is the scan mode's
+ * (fdx_customer_windows_scan computes the windows itself).
+ *   flags & FDX_LAYOUT_GROUPED: ts_d / amount_d are GROUPED (fdx_rekey_payload outputs: row j of
+ * the grouping is ts_d[j], amount_d[j]) -- the layout then reads every segment as a sequential
+ * stream instead of gathering through cperm_d (which still gives irow_d). */
+#define FDX_LAYOUT_GROUPED 1
 size_t fdx_customer_layout_workspace_size(int64_t n_seg);
-int fdx_customer_layout(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                        const int64_t *ts_d, const double *amount_d, int32_t n_windows,
-                        int32_t *sorder_d, uint32_t *goff_d, int64_t *its_d, double *iamt_d,
-                        int32_t *irow_d, int64_t max_slots, int64_t *n_slots_h, void *workspace_d,
-                        size_t workspace_bytes, void *stream);
-/* fdx_customer_layout that also writes every row's window starts (pandas' variable-window
- * start: the first row j of the segment with ts_j > ts_t - window_ns[w], closed='right'),
- * computed in the same kernel from the freshly gathered timestamps, segment-contiguous:
- * row t of segment l of group g at starts_d[w * n_slots + goff_d[g] + l * Lg + t] (Lg = the
- * group's longest segment; starts_d: room for n_windows * max_slots int32).  Follow with
- * fdx_customer_windows_walk. */
-int fdx_customer_layout_starts(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                               const int64_t *ts_d, const double *amount_d, const int64_t *window_ns,
-                               int32_t n_windows, int32_t *sorder_d, uint32_t *goff_d, int64_t *its_d,
-                               double *iamt_d, int32_t *irow_d, int32_t *starts_d, int64_t max_slots,
-                               int64_t *n_slots_h, void *workspace_d, size_t workspace_bytes, void *stream);
+int fdx_customer_layout(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d, const int64_t *ts_d,
+                        const double *amount_d, const int64_t *window_ns /* NULL: no window starts */,
+                        int32_t n_windows, int32_t flags, int32_t *sorder_d, uint32_t *goff_d, int64_t *its_d,
+                        double *iamt_d, int32_t *irow_d, int32_t *starts_d /* with window_ns */, int64_t max_slots,
+                        int64_t *n_slots_h, void *workspace_d, size_t workspace_bytes, void *stream);
 /* The layout in two halves, for callers that overlap them with the re-key:
  * plan -- from the segment offsets alone: sorder_d, goff_d and *n_slots_h (synchronises the
- * stream: the slot count is read back); fill -- fdx_customer_layout_starts_grouped's slots and
- * window starts for that plan (its_d / iamt_d / irow_d of n_slots entries, starts_d of
- * n_windows * n_slots).  fdx_customer_layout* = plan + fill. */
+ * stream: the slot count is read back); fill -- the slots and window starts of the grouped
+ * layout for that plan (its_d / iamt_d / irow_d of n_slots entries, starts_d of
+ * n_windows * n_slots).  fdx_customer_layout = plan + fill. */
 int fdx_customer_layout_plan(const int64_t *seg_off_d, int64_t n_seg, int32_t n_windows, int32_t *sorder_d,
                              uint32_t *goff_d, int64_t *n_slots_h, void *workspace_d, size_t workspace_bytes,
                              void *stream);
@@ -112,42 +112,22 @@ int fdx_customer_layout_plan(const int64_t *seg_off_d, int64_t n_seg, int32_t n_
 int fdx_customer_layout_plan_async(const int64_t *seg_off_d, int64_t n_seg, int32_t n_windows, int32_t *sorder_d,
                                    uint32_t *goff_d, int32_t *plan_h, void *workspace_d, size_t workspace_bytes,
                                    void *stream);
-int fdx_customer_layout_fill_starts_grouped(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                                            const int64_t *gts_d, const double *gamount_d, const int64_t *window_ns,
-                                            int32_t n_windows, const int32_t *sorder_d, const uint32_t *goff_d,
-                                            int64_t n_slots, int64_t *its_d, double *iamt_d, int32_t *irow_d,
-                                            int32_t *starts_d, void *stream);
-/* The fill over fdx_rekey_payload_narrow's outputs: gts_d / gamount_d hold whichever form
- * *narrow_flag_d (device int32) names (narrow_mask: that re-key's, not 0), ts_base_d is that
- * re-key's ts_ns_d (row 0 = the base of the seconds).  its_d, iamt_d, irow_d and starts_d are
- * written bit for bit as fdx_customer_layout_fill_starts_grouped writes them from the 8-byte
- * columns.  One launch: each block loads the flag once and takes the 4-byte or the 8-byte
- * loads, uniformly; a narrow element is widened where it is loaded (ts_base_d[0] + s * 1e9,
- * (double)c / 100.0), so the staged timestamps and the start searches are the wide form's.
- * The windows must be whole seconds (FDX_E_INVALID; fdx_narrow_windows_ok). */
-int fdx_customer_layout_fill_starts_grouped_narrow(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                                                   const void *gts_d, const void *gamount_d,
-                                                   const int64_t *window_ns, int32_t n_windows,
-                                                   const int32_t *sorder_d, const uint32_t *goff_d, int64_t n_slots,
-                                                   int64_t *its_d, double *iamt_d, int32_t *irow_d, int32_t *starts_d,
-                                                   const int32_t *narrow_flag_d, int32_t narrow_mask,
-                                                   const int64_t *ts_base_d, void *stream);
-
-/* fdx_customer_layout_starts over GROUPED ts / amount (fdx_rekey_payload outputs: row j of
- * the grouping is gts_d[j], gamount_d[j]) -- the layout then reads every segment as a
- * sequential stream instead of gathering through cperm_d (which still gives irow_d). */
-int fdx_customer_layout_starts_grouped(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                                       const int64_t *gts_d, const double *gamount_d, const int64_t *window_ns,
-                                       int32_t n_windows, int32_t *sorder_d, uint32_t *goff_d, int64_t *its_d,
-                                       double *iamt_d, int32_t *irow_d, int32_t *starts_d, int64_t max_slots,
-                                       int64_t *n_slots_h, void *workspace_d, size_t workspace_bytes, void *stream);
-/* fdx_customer_layout over GROUPED ts / amount without the window starts (the scan mode's
- * layout: fdx_customer_windows_scan computes the windows itself). */
-int fdx_customer_layout_grouped(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                                const int64_t *gts_d, const double *gamount_d, int32_t n_windows,
-                                int32_t *sorder_d, uint32_t *goff_d, int64_t *its_d, double *iamt_d,
-                                int32_t *irow_d, int64_t max_slots, int64_t *n_slots_h, void *workspace_d,
-                                size_t workspace_bytes, void *stream);
+/* The fill.  narrow_flag_d NULL (narrow_mask then 0, else FDX_E_INVALID): gts_d / gamount_d are
+ * the int64 / float64 columns.  narrow_flag_d given -- the fill over a narrow fdx_rekey_payload's
+ * outputs: gts_d / gamount_d hold whichever form *narrow_flag_d (device int32) names, narrow_mask
+ * is that re-key's (FDX_NARROW_TS or FDX_NARROW_TS | FDX_NARROW_AMOUNT), ts_base_d (not NULL) is
+ * that re-key's pay0_d (row 0 = the base of the seconds), and the windows must be whole seconds
+ * (FDX_E_INVALID; fdx_narrow_windows_ok).  its_d, iamt_d, irow_d and starts_d are written bit for
+ * bit as from the 8-byte columns.  One launch: each block loads the flag once and takes the
+ * 4-byte or the 8-byte loads, uniformly; a narrow element is widened where it is loaded
+ * (ts_base_d[0] + s * 1e9, (double)c / 100.0), so the staged timestamps and the start searches
+ * are the wide form's. */
+int fdx_customer_layout_fill(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d, const void *gts_d,
+                             const void *gamount_d, const int64_t *window_ns, int32_t n_windows,
+                             const int32_t *sorder_d, const uint32_t *goff_d, int64_t n_slots, int64_t *its_d,
+                             double *iamt_d, int32_t *irow_d, int32_t *starts_d,
+                             const int32_t *narrow_flag_d /* NULL: 8-byte columns */, int32_t narrow_mask,
+                             const int64_t *ts_base_d, void *stream);
 /* Customer windows, SCAN mode (SURVEY.md §7 step 4 / §8(b) "exact|scan" mode flag;
  * replaces the same feature_transformation.ipynb:1092-1093 call as fdx_customer_windows):
  * the rolling sums from float64 prefix sums over each segment instead of pandas' sequential
@@ -168,7 +148,7 @@ int fdx_customer_windows_scan(const int64_t *gts_d, const double *gamount_d, con
                               double *val_d, int32_t val_is_sum, void *workspace_d, size_t workspace_bytes,
                               void *stream);
 /* The slot form of the scan mode over a layout built WITH window starts
- * (fdx_customer_layout_starts_grouped): the window starts come from the layout, so the scan
+ * (fdx_customer_layout with window_ns): the window starts come from the layout, so the scan
  * is two coalesced passes -- per-segment prefix sums (grouped order), then NB / SUM by slot.
  * Same outputs and precision as fdx_customer_windows_scan(sorder_d, goff_d, ...); gamount_d
  * grouped; workspace fdx_customer_windows_scan_workspace_size(n, n_seg). */
@@ -177,14 +157,14 @@ int fdx_customer_windows_scan_slots(const double *gamount_d, const int64_t *seg_
                                     int32_t n_windows, const int32_t *starts_d, int32_t *nb_d, double *sum_d,
                                     void *workspace_d, size_t workspace_bytes, void *stream);
 /* The sequential half of fdx_customer_windows_interleaved over the starts of
- * fdx_customer_layout_starts: nb_d / sum_d as there ([W][n_slots] by slot; n_windows >= 3,
+ * fdx_customer_layout (window_ns): nb_d / sum_d as there ([W][n_slots] by slot; n_windows >= 3,
  * i.e. <= 21 segments per wave). */
 int fdx_customer_windows_walk(const double *iamt_d, const int64_t *seg_off_d, const int32_t *sorder_d,
                               const uint32_t *goff_d, int64_t n_seg, int64_t n_slots, int32_t n_windows,
                               const int32_t *starts_d, int32_t *nb_d, double *sum_d, void *stream);
 /* fdx_customer_windows over that layout: nb_d / sum_d are [W][n_slots] indexed by slot, with
  * sum_d the rolling SUM (pandas roll_sum, bit-exact); the average is sum / nb (IEEE float64
- * division, done by the consumer -- fdx_forest_prepare_grouped with cust_val_is_sum = 1 --
+ * division, done by the consumer -- fdx_forest_prepare_grouped with FDX_PREP_VAL_IS_SUM --
  * so that the division is off the sequential recurrence's critical path). */
 int fdx_customer_windows_interleaved(const int64_t *its_d, const double *iamt_d,
                                      const int64_t *seg_off_d, const int32_t *sorder_d,
@@ -231,36 +211,30 @@ int fdx_assemble_features(int64_t n, int32_t n_windows, const double *amount_d,
  * word w = NB_w | FRAUD_w << 32 (both uint32; RISK_w = NB_w > 0 ? (double)FRAUD_w / NB_w : 0,
  * the IEEE division fdx_terminal_windows does; the consumers fdx_forest_prepare_grouped,
  * fdx_forest_prepare_reply and fdx_reply_assemble divide) -- or, when rec_d is NULL,
- * nb_d / risk_d [w*n + q].  runs != 0:
- * segments are concatenations of time-sorted runs (multi-GPU owner side).  scratch_d: int32[n]
- * (prefix fraud counts of segments longer than the kernel's LDS stage, 1,024 rows; such
- * segments cost O(L log L)). */
-int fdx_terminal_windows_grouped(const int64_t *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
+ * nb_d / risk_d [w*n + q].  scratch_d: int32[n] (prefix fraud counts of segments longer than
+ * the kernel's LDS stage, 1,024 rows; such segments cost O(L log L)).
+ *   flags & FDX_TERM_RUNS: segments are concatenations of time-sorted runs (multi-GPU owner side).
+ *   flags & FDX_TERM_COMPACT (n_windows = 3): rec_d is int64[5 n], 16-byte aligned, in the COMPACT
+ * format.  Words [2 r, 2 r + 2) hold row r's record as lo = NB_0 | NB_1 << 21 | NB_2 << 42,
+ * hi = FRAUD_0 | FRAUD_1 << 21 | FRAUD_2 << 42 -- one aligned 16-byte store (and load,
+ * FDX_PREP_TERM_COMPACT) per row instead of a 24-byte record across two.  A row with a window
+ * count above 2^21 - 1 instead gets lo = (1 << 63) | o, hi = 0, with its full 3-word record
+ * (NB | FRAUD << 32 per window) at rec_d[o], o = 2 n + 3 r (the overflow area [2 n, 5 n), written
+ * only for such rows).  Exact for any counts.
+ *   narrow_flag_d (needs FDX_TERM_COMPACT without FDX_TERM_RUNS, n_windows = 3, a whole-second
+ * delay and whole-second windows; FDX_E_INVALID otherwise): gts_d is a narrow fdx_rekey_payload's
+ * ts output -- int32 seconds when *narrow_flag_d == 0 and the int64 column otherwise.  Each block
+ * of the two kernels loads the flag once and takes the 4-byte or the 8-byte loads, uniformly;
+ * seconds are widened to s * 1e9 where they are loaded (the kernels compare differences of
+ * timestamps only, so the common base drops out), and the records are bit for bit those of the
+ * int64 column; closed='right' as before. */
+#define FDX_TERM_RUNS 1
+#define FDX_TERM_COMPACT 2
+int fdx_terminal_windows_grouped(const void *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
                                  const int64_t *seg_off_d, int64_t n_seg, int64_t n, int64_t delay_ns,
-                                 const int64_t *window_ns, int32_t n_windows, int32_t runs, int32_t *nb_d,
-                                 double *risk_d, int64_t *rec_d, int32_t *scratch_d, void *stream);
-/* fdx_terminal_windows_grouped (count records by row) in the COMPACT format, n_windows = 3:
- * rec_d is int64[5 n], 16-byte aligned.  Words [2 r, 2 r + 2) hold row r's record as
- * lo = NB_0 | NB_1 << 21 | NB_2 << 42, hi = FRAUD_0 | FRAUD_1 << 21 | FRAUD_2 << 42 -- one
- * aligned 16-byte store (and load, FDX_PREP_TERM_COMPACT) per row instead of a 24-byte record
- * across two.  A row with a window count above 2^21 - 1 instead gets lo = (1 << 63) | o,
- * hi = 0, with its full 3-word record (NB | FRAUD << 32 per window) at rec_d[o], o = 2 n + 3 r
- * (the overflow area [2 n, 5 n), written only for such rows).  Exact for any counts. */
-int fdx_terminal_windows_grouped_compact(const int64_t *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
-                                         const int64_t *seg_off_d, int64_t n_seg, int64_t n, int64_t delay_ns,
-                                         const int64_t *window_ns, int32_t n_windows, int32_t runs, int64_t *rec_d,
-                                         int32_t *scratch_d, void *stream);
-/* fdx_terminal_windows_grouped_compact (n_windows = 3, single-run segments) over
- * fdx_rekey_payload_narrow's ts output: gts_d holds int32 seconds when *narrow_flag_d == 0 and
- * the int64 column otherwise.  Each block of the two kernels loads the flag once and takes the
- * 4-byte or the 8-byte loads, uniformly; seconds are widened to s * 1e9 where they are loaded
- * (the kernels compare differences of timestamps only, so the common base drops out), and the
- * records are bit for bit those of fdx_terminal_windows_grouped_compact; closed='right' as
- * before.  The delay and the windows must be whole seconds (FDX_E_INVALID otherwise). */
-int fdx_terminal_windows_grouped_narrow(const void *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
-                                        const int64_t *seg_off_d, int64_t n_seg, int64_t n, int64_t delay_ns,
-                                        const int64_t *window_ns, int32_t n_windows, int64_t *rec_d,
-                                        int32_t *scratch_d, const int32_t *narrow_flag_d, void *stream);
+                                 const int64_t *window_ns, int32_t n_windows, int32_t flags, int32_t *nb_d,
+                                 double *risk_d, int64_t *rec_d, int32_t *scratch_d,
+                                 const int32_t *narrow_flag_d /* NULL: int64 gts */, void *stream);
 
 /* ---- a-4: re-key (stable radix sort by key + segment offsets) -------------------------
  * Replaces the regrouping done by pandas groupby('CUSTOMER_ID') / sort_values /
@@ -278,77 +252,76 @@ int fdx_rekey(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys
  * (pay0_d / pay1_d in input row order -> pay0_out_d / pay1_out_d in grouped order), so that the
  * window kernels read the grouped table sequentially.  flag_d (optional, uint8 per row):
  * perm_d[j] = row | (flag_d[row] != 0) << 31 (e.g. TX_FRAUD packed beside the row index).
- * Workspace: fdx_rekey_payload_workspace_size(n, key_bits, number of payload streams). */
+ * Workspace: fdx_rekey_payload_workspace_size(n, key_bits, number of payload streams).
+ * opts (NULL = all zero), each member optional:
+ *   bad_d          receives the number of keys outside [0, n_keys) (zeroed by the call, written on
+ *                  `stream`), counted inside the first radix pass's histogram -- the id range
+ *                  check of the reference's groupby without a kernel of its own.  Out-of-range
+ *                  keys never make the call write out of bounds; the caller raises when *bad_d != 0
+ *                  (the grouping would be wrong), as fdx/ops.py:KeyRangeCheck does.
+ *   sorted_keys_d  receives the sorted keys.  With seg_off_d NULL the workspace is free again when
+ *                  the call's last pass ends, so a second re-key sharing it can start before the
+ *                  offsets are derived (fdx_segment_offsets_sorted, from sorted_keys_d, on any
+ *                  stream ordered after this call).
+ *   hist0_d        the first pass's scanned digit table from fdx_rekey_hist0 over the same keys
+ *                  (hist0_bytes behind it): the first pass goes straight to its scatter.
+ *   narrow_flag_d  the NARROW form: pay0_d = int64 timestamps, pay1_d = float64 amounts or NULL,
+ *                  and the columns narrow_mask names travel through the passes as 4 bytes per row
+ *                  instead of 8 whenever that loses nothing.
+ *     ts      -> int32 seconds relative to pay0_d[0] (read on the device).  Exact iff for every
+ *                row (ts - pay0_d[0]) is a whole number of seconds (1e9 ns) whose quotient fits
+ *                int32; rows out of time order give negative offsets, which is fine.
+ *     amount  -> int32 cents c = rint(a * 100.0).  Exact iff |c| < 2^31 and (double)c / 100.0 has
+ *                the same 64 bits as a -- NaN, +-inf, -0.0 and every non-cent value fail.
+ *                Consumers rebuild a with that same division: bit-identical by construction.
+ *     No pass of its own checks this: the first radix pass reads the 8-byte columns anyway,
+ *     converts while it scatters and stores 1 to *narrow_flag_d (cleared by the call) at the first
+ *     value without a narrow form.  One wide launch of the FIRST pass follows the converting one:
+ *     its blocks return at once while the flag is clear, and redo the pass on the 8-byte columns
+ *     when it is raised (the converting pass itself never returns early).  Every later pass is one
+ *     kernel whose blocks load the flag once and move 4-byte or 8-byte streams, uniformly -- so
+ *     after the call
+ *       *narrow_flag_d == 0: pay0_out_d holds int32 [n] seconds, pay1_out_d int32 [n] cents;
+ *       *narrow_flag_d != 0: they hold the int64 [n] / float64 [n] columns of the wide form.
+ *     Both are buffers of 8 n bytes, and the workspace is the same (the 4-byte streams alias the
+ *     8-byte ones).  perm_d and seg_off_d are the same in both forms.  narrow_mask: which columns
+ *     to try -- FDX_NARROW_TS | FDX_NARROW_AMOUNT, or FDX_NARROW_TS alone (pay1_d then travels as
+ *     8 bytes, unchecked, and pay1_out_d is float64 whatever the flag says: for tables whose
+ *     amounts are known not to be cents, where trying would cost the fallback every time), or 0
+ *     (the caller's windows or delay are not whole seconds, see fdx_narrow_windows_ok): the flag
+ *     is raised from the start and only the wide launches follow.  The consumers take the flag:
+ *     fdx_customer_layout_fill and fdx_terminal_windows_grouped; each block of their kernels
+ *     loads it once.
+ * Which options combine (FDX_E_INVALID otherwise, checked before any work is enqueued):
+ *   bad_d with hist0_d: no -- the count was taken by fdx_rekey_hist0;
+ *   hist0_d: hist0_bytes >= fdx_rekey_hist0_size(n, key_bits);
+ *   sorted_keys_d: 16-byte aligned;
+ *   narrow_flag_d: needs pay0_d, and does not combine with sorted_keys_d;
+ *   narrow_mask: one of the three values above, and 0 when narrow_flag_d is NULL. */
+#define FDX_NARROW_TS 1
+#define FDX_NARROW_AMOUNT 2
+typedef struct {
+    int32_t *bad_d;          /* NULL, or device int32: number of keys outside [0, n_keys) */
+    int32_t *sorted_keys_d;  /* NULL, or int32[n], 16-byte aligned: receives the sorted keys */
+    const void *hist0_d;     /* NULL, or fdx_rekey_hist0's table over the same keys */
+    size_t hist0_bytes;      /* bytes behind hist0_d */
+    int32_t *narrow_flag_d;  /* NULL, or device int32[1]: the narrow re-key (pay0 = ts, pay1 = amount) */
+    int32_t narrow_mask;     /* 0, FDX_NARROW_TS or FDX_NARROW_TS | FDX_NARROW_AMOUNT */
+} fdx_rekey_payload_opts;
 size_t fdx_rekey_payload_workspace_size(int64_t n, int32_t key_bits, int32_t n_payload);
 int fdx_rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys, const uint8_t *flag_d,
-                      const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d, int64_t *seg_off_d,
-                      uint64_t *pay0_out_d, uint64_t *pay1_out_d, void *workspace_d, size_t workspace_bytes,
-                      void *stream);
-/* fdx_rekey_payload that also counts the keys outside [0, n_keys) into *bad_d (device int32,
- * zeroed by the call, written on `stream`) inside the first radix pass's histogram -- the id
- * range check of the reference's groupby without a kernel of its own.  Out-of-range keys never
- * make the call write out of bounds; the caller raises when *bad_d != 0 (the grouping would be
- * wrong), as fdx/ops.py:KeyRangeCheck does. */
-int fdx_rekey_payload_checked(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys,
-                              const uint8_t *flag_d, const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d,
-                              int64_t *seg_off_d, uint64_t *pay0_out_d, uint64_t *pay1_out_d, int32_t *bad_d,
-                              void *workspace_d, size_t workspace_bytes, void *stream);
-/* fdx_rekey_payload_checked (bad_d optional here) with the sorted keys written to the caller's
- * sorted_keys_d (int32 [n], 16-byte aligned) instead of the segment offsets: the workspace is
- * free again when the call's last pass ends, so a second re-key sharing it can start before
- * the offsets are derived (fdx_segment_offsets_sorted, from sorted_keys_d, on any stream
- * ordered after this call). */
-int fdx_rekey_payload_keys(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys, const uint8_t *flag_d,
-                           const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d, int32_t *sorted_keys_d,
-                           uint64_t *pay0_out_d, uint64_t *pay1_out_d, int32_t *bad_d, void *workspace_d,
-                           size_t workspace_bytes, void *stream);
+                      const void *pay0_d, const void *pay1_d, int32_t *perm_d,
+                      int64_t *seg_off_d /* NULL: not derived */, void *pay0_out_d, void *pay1_out_d,
+                      const fdx_rekey_payload_opts *opts /* NULL: none */, void *workspace_d,
+                      size_t workspace_bytes, void *stream);
 /* The first radix pass's scanned digit table of a payload re-key, computed ahead of it (on
  * another stream, e.g. while a re-key that shares the workspace still runs): hist0_d
  * (fdx_rekey_hist0_size bytes, the caller's, not the workspace) also receives the id-range count
- * into bad_d (optional, zeroed by the call) -- the check fdx_rekey_payload_checked does in that
- * pass.  fdx_rekey_payload_hist0 is fdx_rekey_payload whose first pass goes straight to its
- * scatter with that table; keys_d must be unchanged in between. */
+ * into bad_d (optional, zeroed by the call) -- the check fdx_rekey_payload's bad_d does in that
+ * pass.  keys_d must be unchanged until the re-key that takes the table has run. */
 size_t fdx_rekey_hist0_size(int64_t n, int32_t key_bits);
 int fdx_rekey_hist0(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys, void *hist0_d,
                     size_t hist0_bytes, int32_t *bad_d, void *stream);
-int fdx_rekey_payload_hist0(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys, const uint8_t *flag_d,
-                            const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d, int64_t *seg_off_d,
-                            uint64_t *pay0_out_d, uint64_t *pay1_out_d, const void *hist0_d, void *workspace_d,
-                            size_t workspace_bytes, void *stream);
-/* The payload re-key in its NARROW form: the two columns the window kernels read travel through
- * the radix passes as 4 bytes per row instead of 8 whenever that loses nothing.
- *   ts_ns_d   (stream 0, required)  -> int32 seconds relative to ts_ns_d[0] (read on the device).
- *             Exact iff for every row (ts - ts_ns_d[0]) is a whole number of seconds (1e9 ns) whose
- *             quotient fits int32; rows out of time order give negative offsets, which is fine.
- *   amount_d  (stream 1, optional)  -> int32 cents c = rint(a * 100.0).  Exact iff |c| < 2^31 and
- *             (double)c / 100.0 has the same 64 bits as a -- NaN, +-inf, -0.0 and every non-cent
- *             value fail.  Consumers rebuild a with that same division: bit-identical by construction.
- * No pass of its own checks this: the first radix pass reads the 8-byte columns anyway, converts
- * while it scatters and stores 1 to *narrow_flag_d (device int32, cleared by the call) at the first
- * value without a narrow form.  One wide launch of the FIRST pass follows the converting one:
- * its blocks return at once while the flag is clear, and redo the pass on the 8-byte columns when
- * it is raised (the converting pass itself never returns early).  Every later pass is one kernel
- * whose blocks load the flag once and move 4-byte or 8-byte streams, uniformly -- so after the call
- *   *narrow_flag_d == 0: ts_out_d holds int32 [n] seconds, amount_out_d int32 [n] cents;
- *   *narrow_flag_d != 0: they hold the int64 [n] / float64 [n] columns of fdx_rekey_payload.
- * Both are buffers of 8 n bytes, and the workspace is fdx_rekey_payload_workspace_size's (the
- * 4-byte streams alias the 8-byte ones).  perm_d and seg_off_d are the same in both forms.
- * narrow_mask: which columns to try -- FDX_NARROW_TS | FDX_NARROW_AMOUNT, or FDX_NARROW_TS alone
- * (amount_d then travels as 8 bytes, unchecked, and amount_out_d is float64 whatever the flag
- * says: for tables whose amounts are known not to be cents, where trying would cost the fallback
- * every time), or 0 (the caller's windows or delay are not whole seconds, see
- * fdx_narrow_windows_ok): the flag is raised from the start and the call is fdx_rekey_payload.
- * The consumers take the flag: fdx_customer_layout_fill_starts_grouped_narrow and
- * fdx_terminal_windows_grouped_narrow; each block of their kernels loads it once.
- * bad_d (optional): as fdx_rekey_payload_checked.  hist0_d (optional): as fdx_rekey_payload_hist0
- * (then bad_d must be NULL). */
-#define FDX_NARROW_TS 1
-#define FDX_NARROW_AMOUNT 2
-int fdx_rekey_payload_narrow(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys, const uint8_t *flag_d,
-                             const int64_t *ts_ns_d, const double *amount_d, int32_t *perm_d, int64_t *seg_off_d,
-                             void *ts_out_d, void *amount_out_d, int32_t *bad_d, const void *hist0_d,
-                             int32_t *narrow_flag_d, int32_t narrow_mask, void *workspace_d, size_t workspace_bytes,
-                             void *stream);
 /* 1 iff every window and the delay (pass 0 for none) are whole seconds: the narrow consumers
  * compare int32 seconds, which decides as the nanosecond comparison does only then. */
 int fdx_narrow_windows_ok(const int64_t *window_ns, int32_t n_windows, int64_t delay_ns);
@@ -403,7 +376,7 @@ int fdx_scatter(const void *src_d, int32_t elem_bytes, const int32_t *perm_d, in
  * owner rank, owner(t) = t % world.  Per step: fdx_key_map(MOD) -> fdx_rekey(owner) ->
  * fdx_exchange_pack -> RCCL all-to-all (16 B/row) -> fdx_exchange_unpack (local terminal
  * id = t / world) -> fdx_rekey_payload (ts payload, fraud flag) -> fdx_terminal_windows_grouped
- * with runs = 1 (a segment = one time-sorted run per source rank; count records indexed by
+ * with FDX_TERM_RUNS (a segment = one time-sorted run per source rank; count records indexed by
  * receive position) -> RCCL all-to-all back -> fdx_forest_prepare_grouped / fdx_reply_assemble.
  * Record layouts: exchange rec[j] = {ts, term<<32 | fraud<<31 | source row}; reply rows
  * are count records (n_windows words, fdx_terminal_windows_grouped). */
@@ -495,7 +468,7 @@ int fdx_forest_pack_rank2(const fdx_forest_desc *desc, int32_t version, uint32_t
                           double *leaf_value_out, uint8_t *missing_left_out, int32_t *root_out, int32_t *depth_out,
                           float *thr_out, int32_t *thr_off_out /* [33] */, int32_t *slot_feat_out /* [32] */,
                           int32_t *slot_base_out /* [32] */);
-/* Host form of the fused row assembly's search tables (tests; fdx_forest_prepare_grouped*):
+/* Host form of the fused row assembly's search tables (tests; fdx_forest_prepare_grouped):
  * for a 15-feature forest, every 4th v1-layout threshold of features 0, 4, 6, 8 (amount and the
  * three customer averages) as a complete 9-ary tree of 8-key nodes, keys in in-order (= sorted)
  * order, +inf padded.  Feature s's node k (children 9k+1..9k+9) is trees_out[8*(eoff_out[s]+k)
@@ -583,12 +556,10 @@ int fdx_forest_prepare_reply(fdx_forest forest, const int64_t *reply_d, const in
  * with fdx_forest_traverse_perm(out_perm = cust_perm)
  * so that proba lands in row order.  The same call serves the interleaved customer layout
  * (cust_* = slot arrays, cust_perm = irow): slots with cust_perm < 0 are padding (zero
- * row, never written back).  cust_val_is_sum: FDX_PREP_* option bits (1 = cust_avg_d
- * holds rolling sums and the average is computed here as sum / nb; 4 = compact terminal
- * records). */
+ * row, never written back).  opts: FDX_PREP_* option bits. */
 #define FDX_PREP_VAL_IS_SUM 1   /* cust_avg_d holds rolling sums: average = sum / nb here      */
-#define FDX_PREP_TERM_COMPACT 4 /* term_rec_d holds COMPACT records (fdx_terminal_windows_
-                                   grouped_compact; n_windows = 3, 16-byte aligned)          */
+#define FDX_PREP_TERM_COMPACT 4 /* term_rec_d holds COMPACT records (FDX_TERM_COMPACT;
+                                   n_windows = 3, 16-byte aligned)                              */
 #define FDX_PREP_FLAG_CLEARED 8 /* the workspace's NaN flag was cleared by fdx_forest_clear_flag
                                    (earlier, e.g. on another stream): no clearing memset here   */
 #define FDX_PREP_INDEX64 16     /* the row kernel's 64-bit slot arithmetic even where n fits 32 bits
@@ -597,12 +568,6 @@ int fdx_forest_prepare_reply(fdx_forest forest, const int64_t *reply_d, const in
  * FDX_PREP_FLAG_CLEARED, the prepare call that follows skips its own clearing -- the scoring step
  * enqueues this off its critical path (fdx.pipeline). */
 int fdx_forest_clear_flag(fdx_forest forest, int64_t n, void *workspace_d, size_t workspace_bytes, void *stream);
-int fdx_forest_prepare_grouped(fdx_forest forest, int64_t n, int32_t n_windows, int32_t flags_mode,
-                               int32_t cust_val_is_sum, const int64_t *cust_ts_d, const double *cust_amount_d,
-                               const int32_t *cust_nb_d, const double *cust_avg_d,
-                               const int32_t *cust_perm_d, const int32_t *term_inv_d,
-                               const int64_t *term_rec_d, void *workspace_d, size_t workspace_bytes,
-                               void *stream);
 /* The featurized table the reference writes (feature_transformation.ipynb:2890-2905; columns
  * added at :613-622 and :1509-1520): one 80-byte record per transaction in the compact form of
  * SURVEY §8(d) -- window counts as int32 (pandas holds the same integers as float64),
@@ -617,7 +582,7 @@ typedef struct fdx_feature_row {
     uint8_t pad[2];
     int32_t row;            /* input row of the transaction (-1: a padding slot's record) */
 } fdx_feature_row;
-/* rows_order of fdx_forest_prepare_grouped_rows */
+/* rows_order of fdx_forest_prepare_grouped */
 #define FDX_ROWS_INPUT_ORDER 1 /* out_d = fdx_feature_row records, out_d[r] = input row r (time order,
                                   as the reference's table after its sort_values('TX_DATETIME')):
                                   one random 80-byte write per row (rows >= out_cap: not written) */
@@ -631,17 +596,15 @@ typedef struct fdx_feature_row {
     ((c) < 6 ? (int64_t)(c) * 4 * (cap) : (c) < 12 ? (int64_t)24 * (cap) + ((c) - 6) * (int64_t)8 * (cap) \
                                        : (c) == 12 ? (int64_t)72 * (cap) : (int64_t)76 * (cap))
 #define FDX_FEATURE_TABLE_BYTES(cap) ((int64_t)78 * (cap))
-/* fdx_forest_prepare_grouped that also writes the featurized table, in rows_order, with the
- * same values the scoring row is built from (n_windows = 3 and the rank layout; other shapes:
- * FDX_E_UNSUPPORTED).  out_d NULL = fdx_forest_prepare_grouped; out_cap = records (input order)
- * or rows per column (slot order) the buffer holds. */
-int fdx_forest_prepare_grouped_rows(fdx_forest forest, int64_t n, int32_t n_windows, int32_t flags_mode,
-                                    int32_t cust_val_is_sum, const int64_t *cust_ts_d,
-                                    const double *cust_amount_d, const int32_t *cust_nb_d,
-                                    const double *cust_avg_d, const int32_t *cust_perm_d,
-                                    const int32_t *term_inv_d, const int64_t *term_rec_d, void *out_d,
-                                    int64_t out_cap, int32_t rows_order, void *workspace_d, size_t workspace_bytes,
-                                    void *stream);
+/* With out_d, the same pass also writes the featurized table, in rows_order, with the same values
+ * the scoring row is built from (n_windows = 3 and the rank layout; other shapes:
+ * FDX_E_UNSUPPORTED).  out_d NULL = no table; out_cap = records (input order) or rows per column
+ * (slot order) the buffer holds. */
+int fdx_forest_prepare_grouped(fdx_forest forest, int64_t n, int32_t n_windows, int32_t flags_mode, int32_t opts,
+                               const int64_t *cust_ts_d, const double *cust_amount_d, const int32_t *cust_nb_d,
+                               const double *cust_avg_d, const int32_t *cust_perm_d, const int32_t *term_inv_d,
+                               const int64_t *term_rec_d, void *out_d, int64_t out_cap, int32_t rows_order,
+                               void *workspace_d, size_t workspace_bytes, void *stream);
 /* fdx_forest_traverse writing proba_d[out_perm_d[row]] (and leaf rows likewise). */
 int fdx_forest_traverse_perm(fdx_forest forest, int64_t n, double *proba_d, const int32_t *out_perm_d,
                              int32_t *leaf_d, void *workspace_d, size_t workspace_bytes, void *stream);
@@ -660,7 +623,7 @@ int fdx_segment_latest(const int64_t *ts_d, const int32_t *perm_d, const int64_t
 int fdx_segment_first_in_range(const int64_t *ts_d, const int32_t *perm_d, const int64_t *seg_off_d,
                                int64_t n_seg, int64_t t_lo, int64_t t_hi, int32_t *out_row_d, void *stream);
 /* The same two snapshots straight from the featurized table the scoring path writes
- * (fdx_forest_prepare_grouped_rows, FDX_ROWS_SLOT_ORDER: row_d = its FDX_FEATURE_COL(12) column,
+ * (fdx_forest_prepare_grouped, FDX_ROWS_SLOT_ORDER: row_d = its FDX_FEATURE_COL(12) column,
  * slot -> input row, -1 = padding), input rows in time order; ts_d / key_d by input row:
  *   FDX_SELECT_LATEST:         out_slot_d[k] = the slot of the first input row holding key k's
  *                              maximum ts (groupby(key).TX_DATETIME.idxmax(), :2914-2918)
@@ -723,7 +686,7 @@ int fdx_cdc_compact(const uint8_t *keep_d, int64_t n, const int64_t *customer_d,
  *   term_rec_d[r][W] (NB | FRAUD << 32, as fdx_terminal_windows_grouped) for the multi-GPU
  *   return exchange.  When cust_nb_d / cust_sum_d are given, the customer half goes there
  *   instead ([W][n] planes: NB int32 and the rolling SUM, bit-exact pandas roll_sum), and X_d
- *   may be NULL: the scoring layout of fdx_forest_prepare_grouped (cust_val_is_sum = 1,
+ *   may be NULL: the scoring layout of fdx_forest_prepare_grouped (opts = FDX_PREP_VAL_IS_SUM,
  *   cust_perm_d = NULL, term_inv_d = NULL, cust_ts_d / cust_amount_d = the batch's ts / amount).
  *   Asynchronous; errors inside the kernels are collected as bits:
  * fdx_stream_status: synchronises, returns and clears them (1 customer ring overflow, 2

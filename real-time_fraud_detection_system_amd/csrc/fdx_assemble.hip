@@ -6,7 +6,7 @@
 // Replaces loaded_scaler.transform (pyspark/scripts/fraud_detection.py:190; shared_functions.py
 // :114-120) and the feature assembly of feature_transformation.ipynb:2890-2905 / the UDF frame of
 // fraud_detection.py:183-189; optionally writes the featurized table itself
-// (fdx_forest_prepare_grouped_rows).
+// (fdx_forest_prepare_grouped).
 #include "fdx_forest_internal.h"
 
 namespace fdx {
@@ -641,7 +641,7 @@ struct PrepRow {
 // The feature table is stored behind the row's segment / ratio loads (r04: right after the row's
 // loads or after the rank row measured slower), by nontemporal stores, and the row loop runs its
 // first iteration peeled.
-// EMIT: the featurized table besides the rank rows (fdx_forest_prepare_grouped_rows): 0 = none,
+// EMIT: the featurized table besides the rank rows (fdx_forest_prepare_grouped): 0 = none,
 // FDX_ROWS_INPUT_ORDER / FDX_ROWS_SLOT_ORDER = the fdx_feature_row record of each slot's row at its
 // input row / at its slot, stored as soon as the row's values are loaded (the record's registers
 // die before the rank search; kept to the end, 15 VGPRs spilled)
@@ -1180,23 +1180,12 @@ extern "C" int fdx_forest_clear_flag(fdx_forest F, int64_t n, void *ws, size_t w
     return FDX_OK;
 }
 
-extern "C" int fdx_forest_prepare_grouped(fdx_forest F, int64_t n, int32_t n_windows, int32_t flags_mode,
-                                          int32_t cust_val_is_sum, const int64_t *cust_ts_d, const double *cust_amount_d,
+extern "C" int fdx_forest_prepare_grouped(fdx_forest F, int64_t n, int32_t n_windows, int32_t flags_mode, int32_t opts,
+                                          const int64_t *cust_ts_d, const double *cust_amount_d,
                                           const int32_t *cust_nb_d, const double *cust_avg_d,
                                           const int32_t *cust_perm_d, const int32_t *term_inv_d,
-                                          const int64_t *term_rec_d, void *ws, size_t ws_bytes, void *stream) {
-    return fdx_forest_prepare_grouped_rows(F, n, n_windows, flags_mode, cust_val_is_sum, cust_ts_d, cust_amount_d,
-                                           cust_nb_d, cust_avg_d, cust_perm_d, term_inv_d, term_rec_d, nullptr, 0, 0,
-                                           ws, ws_bytes, stream);
-}
-
-extern "C" int fdx_forest_prepare_grouped_rows(fdx_forest F, int64_t n, int32_t n_windows, int32_t flags_mode,
-                                               int32_t cust_val_is_sum, const int64_t *cust_ts_d,
-                                               const double *cust_amount_d, const int32_t *cust_nb_d,
-                                               const double *cust_avg_d, const int32_t *cust_perm_d,
-                                               const int32_t *term_inv_d, const int64_t *term_rec_d, void *rows_out_d,
-                                               int64_t out_cap, int32_t rows_order, void *ws, size_t ws_bytes,
-                                               void *stream) {
+                                          const int64_t *term_rec_d, void *rows_out_d, int64_t out_cap,
+                                          int32_t rows_order, void *ws, size_t ws_bytes, void *stream) {
     FDX_REQUIRE(F, "null forest");
     FDX_REQUIRE(!rows_out_d || rows_order == FDX_ROWS_INPUT_ORDER || rows_order == FDX_ROWS_SLOT_ORDER,
                 "rows_order must be FDX_ROWS_INPUT_ORDER or FDX_ROWS_SLOT_ORDER");
@@ -1212,10 +1201,9 @@ extern "C" int fdx_forest_prepare_grouped_rows(fdx_forest F, int64_t n, int32_t 
                 3 + 4 * n_windows);
     if (n == 0) return FDX_OK;
     FDX_REQUIRE(cust_ts_d && cust_amount_d && cust_nb_d && cust_avg_d && term_rec_d, "null pointer");
-    FDX_REQUIRE((cust_val_is_sum & ~29) == 0,
-                "cust_val_is_sum: FDX_PREP_VAL_IS_SUM | FDX_PREP_TERM_COMPACT | FDX_PREP_FLAG_CLEARED | "
-                "FDX_PREP_INDEX64 only");
-    FDX_REQUIRE(!(cust_val_is_sum & 4) || (n_windows == 3 && ((uintptr_t)term_rec_d & 15) == 0),
+    FDX_REQUIRE((opts & ~29) == 0,
+                "opts: FDX_PREP_VAL_IS_SUM | FDX_PREP_TERM_COMPACT | FDX_PREP_FLAG_CLEARED | FDX_PREP_INDEX64 only");
+    FDX_REQUIRE(!(opts & 4) || (n_windows == 3 && ((uintptr_t)term_rec_d & 15) == 0),
                 "compact terminal records: W = 3 and a 16-byte aligned record array");
     float *z;
     double *acc;
@@ -1223,17 +1211,17 @@ extern "C" int fdx_forest_prepare_grouped_rows(fdx_forest F, int64_t n, int32_t 
     int rc = forest_ws(F, n, ws, ws_bytes, &z, &acc, &flag);
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
-    if (!(cust_val_is_sum & FDX_PREP_FLAG_CLEARED)) FDX_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
-    cust_val_is_sum &= ~FDX_PREP_FLAG_CLEARED;
-    const bool index64 = (cust_val_is_sum & FDX_PREP_INDEX64) != 0;
-    cust_val_is_sum &= ~FDX_PREP_INDEX64;
+    if (!(opts & FDX_PREP_FLAG_CLEARED)) FDX_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
+    opts &= ~FDX_PREP_FLAG_CLEARED;
+    const bool index64 = (opts & FDX_PREP_INDEX64) != 0;
+    opts &= ~FDX_PREP_INDEX64;
     const unsigned grid = stream_grid(n, 256);
     const RankTab rt = rank_tab(F);
     if (rank_mode(F) && n_windows == 3 && rt.rat && rt.etab) {
 #define FDX_ZFILL_W3_I(E, C, T, I)                                                                                \
     hipLaunchKernelGGL((k_zfill_grouped_w3<E, C, T, I>), dim3(grid_w3), dim3(kW3Block), 0, st, cust_ts_d,          \
                        cust_amount_d, cust_nb_d, cust_avg_d, cust_perm_d, term_inv_d, term_rec_d, n, flags_mode,    \
-                       cust_val_is_sum, F->mean_d, F->scale_d, (void *)z, flag, rt,                                 \
+                       opts, F->mean_d, F->scale_d, (void *)z, flag, rt,                                            \
                        reinterpret_cast<char *>(rows_out_d), out_cap)
 #define FDX_ZFILL_W3(E, C, T)                                                                                     \
     do {                                                                                                          \
@@ -1241,7 +1229,7 @@ extern "C" int fdx_forest_prepare_grouped_rows(fdx_forest F, int64_t n, int32_t 
     } while (0)
 #define FDX_ZFILL_W3_E(E)                                                                                         \
     do {                                                                                                          \
-        if (cust_val_is_sum & 4) {                                                                                \
+        if (opts & 4) {                                                                                           \
             if (term_inv_d) FDX_ZFILL_W3(E, true, true); else FDX_ZFILL_W3(E, true, false);                       \
         } else {                                                                                                  \
             if (term_inv_d) FDX_ZFILL_W3(E, false, true); else FDX_ZFILL_W3(E, false, false);                     \
@@ -1265,15 +1253,15 @@ extern "C" int fdx_forest_prepare_grouped_rows(fdx_forest F, int64_t n, int32_t 
     // (the wide layout, or a forest whose searched features outgrow the S-trees' LDS budget)
     FDX_REQUIRE(!rows_out_d || n_windows == 3, "the featurized table has 3 windows (n_windows = %d)", n_windows);
     FDX_PREP(k_zfill_grouped, dim3(grid), st, cust_ts_d, cust_amount_d, cust_nb_d, cust_avg_d, cust_perm_d,
-             term_inv_d, term_rec_d, n, n_windows, flags_mode, cust_val_is_sum, F->mean_d, F->scale_d, (void *)z, flag);
+             term_inv_d, term_rec_d, n, n_windows, flags_mode, opts, F->mean_d, F->scale_d, (void *)z, flag);
     FDX_LAUNCHED("k_zfill_grouped");
     if (rows_out_d) {
         char *feat = reinterpret_cast<char *>(rows_out_d);
-        const int32_t vs = cust_val_is_sum & 1;
+        const int32_t vs = opts & 1;
 #define FDX_ROWS_K(E, C)                                                                                          \
     hipLaunchKernelGGL((k_feature_rows<E, C>), dim3(stream_grid(n, 256)), dim3(256), 0, st, cust_ts_d, cust_nb_d,  \
                        cust_avg_d, cust_perm_d, term_inv_d, term_rec_d, n, flags_mode, vs, feat, out_cap)
-        const bool compact = (cust_val_is_sum & 4) != 0;
+        const bool compact = (opts & 4) != 0;
         if (rows_order == FDX_ROWS_SLOT_ORDER) {
             if (compact) FDX_ROWS_K(FDX_ROWS_SLOT_ORDER, true); else FDX_ROWS_K(FDX_ROWS_SLOT_ORDER, false);
         } else {

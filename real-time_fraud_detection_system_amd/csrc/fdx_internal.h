@@ -63,7 +63,7 @@ __device__ __forceinline__ double term_risk(int64_t w) {
     return nb > 0 ? (double)fr / (double)nb : 0.0;
 }
 
-// COMPACT count records (fdx_terminal_windows_grouped_compact, W = 3): 16 bytes per row,
+// COMPACT count records (fdx_terminal_windows_grouped + FDX_TERM_COMPACT, W = 3): 16 bytes per row,
 // lo = NB_0 | NB_1 << 21 | NB_2 << 42, hi = FRAUD_0 | FRAUD_1 << 21 | FRAUD_2 << 42 (one
 // aligned 16-byte access instead of a 24-byte record over two).  A row whose window count
 // does not fit 21 bits has bit 63 of lo set and the low 63 bits = the word offset, from the

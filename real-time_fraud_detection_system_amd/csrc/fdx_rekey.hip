@@ -139,7 +139,7 @@ __device__ __forceinline__ uint32_t digit_of(K k, int shift, K flip) {
 // PMC); each key is one LDS atomic add on them (the ballot multisplit -- only the lowest lane
 // of each group of equal digits adds the group's size -- took BITS ballots per key, which the
 // counts alone do not need: re-keys 0.585 / 0.553 -> 0.553 / 0.534 ms, r03am_radix_hist_ab.txt).
-// bad != nullptr (first pass of fdx_rekey_payload_checked): also count the keys >= key_limit
+// bad != nullptr (first pass of fdx_rekey_payload with bad_d): also count the keys >= key_limit
 // (as unsigned: negative int32 ids count too) -- the id range check rides on this pass's reads.
 template <typename K, int BITS>
 __global__ void __launch_bounds__(kBlock) k_radix_hist(const K *__restrict__ keys, int64_t n, int shift,
@@ -211,7 +211,7 @@ inline unsigned scatter_grid(int64_t n_tiles) { return (unsigned)((n_tiles + 7) 
 //
 // scatter_one_tile is the tile's work; k_radix_scatter (one tile per block, 8-byte streams) and
 // k_radix_scatter_narrow (the forms below) are its kernels.
-// PM: the payload form (fdx_rekey_payload_narrow; nflag = its device flag, 0 = narrow holds).
+// PM: the payload form (fdx_rekey_payload's narrow_flag_d: nflag = that device flag, 0 = narrow holds).
 //   kPayWide       8-byte streams in and out (nflag unused): k_radix_scatter.
 //   kPayConvert    the first pass of the narrow form: reads the 8-byte columns (stream 0 = int64
 //                  timestamps, stream 1 = float64 amounts), writes 4-byte streams (narrow_ts /
@@ -530,7 +530,7 @@ __global__ void k_copy_u32(const uint32_t *__restrict__ in, uint32_t *__restrict
 // (sk[n-1], n_keys].  Each q is written once when the keys are sorted and in range.  (Three
 // launches before -- fill -1, mark the present keys, binary-search the absent ones.)  The buffer
 // is zeroed first, so that out-of-range ids -- which sort out of key order and are rejected
-// after the step (fdx_rekey_payload_checked) -- can never leave an offset outside [0, n].
+// after the step (fdx_rekey_payload's bad_d) -- can never leave an offset outside [0, n].
 __device__ __forceinline__ void seg_bound(int64_t i, int64_t prev, int64_t cur, int64_t n_keys,
                                           int64_t *__restrict__ seg_off) {
     const int64_t q1 = min(cur, n_keys);
@@ -861,41 +861,6 @@ extern "C" size_t fdx_rekey_payload_workspace_size(int64_t n, int32_t key_bits, 
     return sort_ws<uint32_t>(n, nullptr, nullptr, n_payload < 0 ? 0 : (n_payload > 2 ? 2 : n_payload));
 }
 
-static int rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys, const uint8_t *flag_d,
-                         const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d, int64_t *seg_off_d,
-                         uint64_t *pay0_out_d, uint64_t *pay1_out_d, int32_t *bad_d, void *workspace_d,
-                         size_t workspace_bytes, void *stream, int32_t *sorted_keys_d = nullptr,
-                         const uint32_t *hist0_d = nullptr, int32_t *nflag_d = nullptr, int32_t narrow_mask = 0);
-
-extern "C" int fdx_rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys,
-                                 const uint8_t *flag_d, const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d,
-                                 int64_t *seg_off_d, uint64_t *pay0_out_d, uint64_t *pay1_out_d, void *workspace_d,
-                                 size_t workspace_bytes, void *stream) {
-    return rekey_payload(keys_d, n, key_bits, n_keys, flag_d, pay0_d, pay1_d, perm_d, seg_off_d, pay0_out_d,
-                         pay1_out_d, nullptr, workspace_d, workspace_bytes, stream);
-}
-
-extern "C" int fdx_rekey_payload_checked(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys,
-                                         const uint8_t *flag_d, const uint64_t *pay0_d, const uint64_t *pay1_d,
-                                         int32_t *perm_d, int64_t *seg_off_d, uint64_t *pay0_out_d,
-                                         uint64_t *pay1_out_d, int32_t *bad_d, void *workspace_d,
-                                         size_t workspace_bytes, void *stream) {
-    FDX_REQUIRE(bad_d, "null bad_d");
-    return rekey_payload(keys_d, n, key_bits, n_keys, flag_d, pay0_d, pay1_d, perm_d, seg_off_d, pay0_out_d,
-                         pay1_out_d, bad_d, workspace_d, workspace_bytes, stream);
-}
-
-extern "C" int fdx_rekey_payload_keys(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys,
-                                      const uint8_t *flag_d, const uint64_t *pay0_d, const uint64_t *pay1_d,
-                                      int32_t *perm_d, int32_t *sorted_keys_d, uint64_t *pay0_out_d,
-                                      uint64_t *pay1_out_d, int32_t *bad_d, void *workspace_d, size_t workspace_bytes,
-                                      void *stream) {
-    FDX_REQUIRE(n == 0 || sorted_keys_d, "null sorted_keys_d");
-    FDX_REQUIRE(((uintptr_t)sorted_keys_d & 15) == 0, "sorted_keys_d must be 16-byte aligned");
-    return rekey_payload(keys_d, n, key_bits, n_keys, flag_d, pay0_d, pay1_d, perm_d, nullptr, pay0_out_d,
-                         pay1_out_d, bad_d, workspace_d, workspace_bytes, stream, sorted_keys_d);
-}
-
 extern "C" size_t fdx_rekey_hist0_size(int64_t n, int32_t key_bits) {
     if (n < 0) n = 0;
     int passes, n9;
@@ -924,34 +889,6 @@ extern "C" int fdx_rekey_hist0(const int32_t *keys_d, int64_t n, int32_t key_bit
                                  (uint64_t)n_keys, bad_d, st);
 }
 
-extern "C" int fdx_rekey_payload_hist0(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys,
-                                       const uint8_t *flag_d, const uint64_t *pay0_d, const uint64_t *pay1_d,
-                                       int32_t *perm_d, int64_t *seg_off_d, uint64_t *pay0_out_d, uint64_t *pay1_out_d,
-                                       const void *hist0_d, void *workspace_d, size_t workspace_bytes, void *stream) {
-    FDX_REQUIRE(n == 0 || hist0_d, "null hist0_d");
-    return rekey_payload(keys_d, n, key_bits, n_keys, flag_d, pay0_d, pay1_d, perm_d, seg_off_d, pay0_out_d,
-                         pay1_out_d, nullptr, workspace_d, workspace_bytes, stream, nullptr,
-                         reinterpret_cast<const uint32_t *>(hist0_d));
-}
-
-extern "C" int fdx_rekey_payload_narrow(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys,
-                                        const uint8_t *flag_d, const int64_t *ts_ns_d, const double *amount_d,
-                                        int32_t *perm_d, int64_t *seg_off_d, void *ts_out_d, void *amount_out_d,
-                                        int32_t *bad_d, const void *hist0_d, int32_t *narrow_flag_d,
-                                        int32_t narrow_mask, void *workspace_d, size_t workspace_bytes,
-                                        void *stream) {
-    FDX_REQUIRE(narrow_flag_d, "null narrow_flag_d");
-    FDX_REQUIRE(narrow_mask == 0 || narrow_mask == FDX_NARROW_TS || narrow_mask == (FDX_NARROW_TS | FDX_NARROW_AMOUNT),
-                "narrow_mask: 0, FDX_NARROW_TS or FDX_NARROW_TS | FDX_NARROW_AMOUNT");
-    FDX_REQUIRE(n == 0 || ts_ns_d, "the narrow re-key carries at least the timestamps");
-    FDX_REQUIRE(!(bad_d && hist0_d), "the id-range count is taken by fdx_rekey_hist0 when hist0_d is given");
-    return rekey_payload(keys_d, n, key_bits, n_keys, flag_d, reinterpret_cast<const uint64_t *>(ts_ns_d),
-                         reinterpret_cast<const uint64_t *>(amount_d), perm_d, seg_off_d,
-                         reinterpret_cast<uint64_t *>(ts_out_d), reinterpret_cast<uint64_t *>(amount_out_d), bad_d,
-                         workspace_d, workspace_bytes, stream, nullptr, reinterpret_cast<const uint32_t *>(hist0_d),
-                         narrow_flag_d, narrow_mask);
-}
-
 extern "C" int fdx_narrow_windows_ok(const int64_t *window_ns, int32_t n_windows, int64_t delay_ns) {
     if (!window_ns || n_windows < 1 || delay_ns % kNsPerSec != 0) return 0;
     for (int i = 0; i < n_windows; ++i)
@@ -972,18 +909,32 @@ extern "C" int fdx_segment_offsets_sorted(const int32_t *sorted_keys_d, int64_t 
     return seg_offsets(reinterpret_cast<const uint32_t *>(sorted_keys_d), n, n_keys, seg_off_d, st);
 }
 
-static int rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys, const uint8_t *flag_d,
-                         const uint64_t *pay0_d, const uint64_t *pay1_d, int32_t *perm_d, int64_t *seg_off_d,
-                         uint64_t *pay0_out_d, uint64_t *pay1_out_d, int32_t *bad_d, void *workspace_d,
-                         size_t workspace_bytes, void *stream, int32_t *sorted_keys_d,
-                         const uint32_t *hist0_d, int32_t *nflag_d, int32_t narrow_mask) {
-    const bool allow_narrow = (narrow_mask & 1) != 0;
+extern "C" int fdx_rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int64_t n_keys,
+                                 const uint8_t *flag_d, const void *pay0_d, const void *pay1_d, int32_t *perm_d,
+                                 int64_t *seg_off_d, void *pay0_out_d, void *pay1_out_d,
+                                 const fdx_rekey_payload_opts *opts, void *workspace_d, size_t workspace_bytes,
+                                 void *stream) {
+    const fdx_rekey_payload_opts o = opts ? *opts : fdx_rekey_payload_opts{};
+    int32_t *const bad_d = o.bad_d, *const nflag_d = o.narrow_flag_d;
+    const uint32_t *const hist0_d = reinterpret_cast<const uint32_t *>(o.hist0_d);
+    const int32_t narrow_mask = o.narrow_mask;
+    const bool allow_narrow = (narrow_mask & FDX_NARROW_TS) != 0;
     FDX_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX, "n out of range");
     FDX_REQUIRE(key_bits >= 1 && key_bits <= 31, "key_bits must be in [1, 31]");
     FDX_REQUIRE(n_keys >= 1 && n_keys <= (int64_t(1) << key_bits), "n_keys must be in [1, 2^key_bits]");
     FDX_REQUIRE((pay0_d == nullptr) == (pay0_out_d == nullptr) && (pay1_d == nullptr) == (pay1_out_d == nullptr) &&
                     (pay1_d == nullptr || pay0_d != nullptr),
                 "payload inputs and outputs go together (stream 1 needs stream 0)");
+    // which options combine (fdx.h)
+    FDX_REQUIRE(!(bad_d && hist0_d), "bad_d: the id-range count is taken by fdx_rekey_hist0 when hist0_d is given");
+    FDX_REQUIRE(!hist0_d || o.hist0_bytes >= fdx_rekey_hist0_size(n, key_bits),
+                "hist0_bytes: %zu < fdx_rekey_hist0_size = %zu", o.hist0_bytes, fdx_rekey_hist0_size(n, key_bits));
+    FDX_REQUIRE(((uintptr_t)o.sorted_keys_d & 15) == 0, "sorted_keys_d must be 16-byte aligned");
+    FDX_REQUIRE(!nflag_d || n == 0 || pay0_d, "narrow_flag_d: the narrow re-key carries at least the timestamps, pay0_d");
+    FDX_REQUIRE(!(nflag_d && o.sorted_keys_d), "narrow_flag_d does not combine with sorted_keys_d");
+    FDX_REQUIRE(narrow_mask == 0 || narrow_mask == FDX_NARROW_TS || narrow_mask == (FDX_NARROW_TS | FDX_NARROW_AMOUNT),
+                "narrow_mask: 0, FDX_NARROW_TS or FDX_NARROW_TS | FDX_NARROW_AMOUNT");
+    FDX_REQUIRE(nflag_d || narrow_mask == 0, "narrow_mask needs narrow_flag_d");
     hipStream_t st = as_stream(stream);
     if (bad_d && !hist0_d) FDX_HIP(hipMemsetAsync(bad_d, 0, sizeof(int32_t), st));  // (hist0: counted there)
     // the narrow flag: clear = the 4-byte forms hold (the first pass raises it); not allowed, or
@@ -1001,14 +952,14 @@ static int rekey_payload(const int32_t *keys_d, int64_t n, int32_t key_bits, int
         set_error("rekey workspace too small: %zu < %zu", workspace_bytes, need);
         return FDX_E_WORKSPACE;
     }
-    const uint64_t *pin[2] = {pay0_d, pay1_d};
-    uint64_t *pout[2] = {pay0_out_d, pay1_out_d};
+    const uint64_t *pin[2] = {reinterpret_cast<const uint64_t *>(pay0_d), reinterpret_cast<const uint64_t *>(pay1_d)};
+    uint64_t *pout[2] = {reinterpret_cast<uint64_t *>(pay0_out_d), reinterpret_cast<uint64_t *>(pay1_out_d)};
     const uint32_t *sorted = nullptr;
-    uint32_t *kout = reinterpret_cast<uint32_t *>(sorted_keys_d);
+    uint32_t *kout = reinterpret_cast<uint32_t *>(o.sorted_keys_d);
     int rc = radix_sort<uint32_t>(reinterpret_cast<const uint32_t *>(keys_d), n, key_bits, 0u, kout,
                                   reinterpret_cast<uint32_t *>(perm_d), w, st, &sorted, pw, flag_d, pin, pout,
                                   (uint64_t)n_keys, hist0_d ? nullptr : bad_d, hist0_d,
-                                  allow_narrow ? nflag_d : nullptr, (narrow_mask & 2) != 0);
+                                  allow_narrow ? nflag_d : nullptr, (narrow_mask & FDX_NARROW_AMOUNT) != 0);
     if (rc) return rc;
     if (kout && sorted != kout) {  // (no radix pass: the input order is the sorted one)
         hipLaunchKernelGGL(k_copy_u32, dim3(stream_grid(n, 256)), dim3(256), 0, st, sorted, kout, n);

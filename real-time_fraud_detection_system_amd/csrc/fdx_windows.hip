@@ -385,7 +385,7 @@ __global__ void __launch_bounds__(kPlanWaves * kWave) k_layout_plan_small(const 
 // GROUPED: ts / amount are already in grouped order (fdx_rekey_payload carried them through
 // the re-key): slot (t, l) reads ts[seg_off[s] + t] -- each segment a sequential stream --
 // instead of ts[cperm[...]], a random HBM line per 8-byte element.
-// NARROW (fdx_rekey_payload_narrow's outputs; nflag = its device flag, loaded once per block):
+// NARROW (a narrow fdx_rekey_payload's outputs; nflag = its device flag, loaded once per block):
 // flag clear, ts is int32 seconds relative to tbase[0] and amount int32 cents, and every element
 // is widened where it is loaded (tbase[0] + s * 1e9 and (double)c / 100.0: the input's own bits)
 // -- the slots, the staged timestamps and the searches are then what they are from the 8-byte
@@ -1310,7 +1310,7 @@ __device__ __forceinline__ void term_emit(int32_t *nb_out, double *risk_out, int
 // (> 64 in LDS, > 2 LR - 1 long -- never the owner side, which has one run per source rank)
 // is counted directly, O(L) per row.  Only segments with len_lo < L <= len_hi are processed
 // (the short / long passes of terminal_launch).
-// NARROW (fdx_rekey_payload_narrow's ts output; nflag = its device flag, loaded once per block):
+// NARROW (a narrow fdx_rekey_payload's ts output; nflag = its device flag, loaded once per block):
 // flag clear, gts is int32 seconds relative to a base common to all rows, widened to s * 1e9
 // where it is loaded -- the kernel compares differences of timestamps only, so the base drops
 // out and every search decides as on the int64 column; flag raised, gts is that column.
@@ -1829,7 +1829,7 @@ extern "C" int fdx_customer_windows(const int64_t *ts_ns_d, const double *amount
 // Every terminal-window launch: the short-segment pass (<= kTermShortRows rows, small LDS
 // stage, more resident waves) then the long pass (the 1,024-row stage, global memory beyond);
 // each skips the other's segments.
-// nflag (runs == false): gts is fdx_rekey_payload_narrow's output, in the form the flag names.
+// nflag (runs == false): gts is a narrow fdx_rekey_payload's output, in the form the flag names.
 static void terminal_launch(bool runs, const int64_t *gts, const uint8_t *gfr, const int32_t *rows,
                             const int64_t *seg_off, int64_t n_seg, int64_t n, int64_t delay_ns, const WinArgs &wa,
                             int32_t n_windows, int32_t *nb_d, double *risk_d, int64_t *rec_d, int32_t *scratch,
@@ -1844,7 +1844,7 @@ static void terminal_launch(bool runs, const int64_t *gts, const uint8_t *gfr, c
         FDX_TERM_LAUNCH(true, kTermShortRows, 0, kTermShortRows);
         FDX_TERM_LAUNCH(true, kTermLdsRows, lo, inf);
     } else {
-        if (nflag) {  // (n_windows == 3: terminal_grouped requires it)
+        if (nflag) {  // (n_windows == 3: fdx_terminal_windows_grouped requires it)
             hipLaunchKernelGGL(k_terminal_short_narrow<3>, dim3(grid), dim3(kTermBlock), 0, st, gts, gfr, rows, seg_off,
                                n_seg, n, delay_ns, wa, n_windows, nb_d, risk_d, rec_d, compact_n, nflag);
             hipLaunchKernelGGL(k_terminal_g_narrow<kTermLdsRows>, dim3(grid), dim3(kTermBlock), 0, st, gts, gfr, rows,
@@ -1890,14 +1890,16 @@ extern "C" int fdx_terminal_windows(const int64_t *ts_ns_d, const uint8_t *fraud
     return FDX_OK;
 }
 
-static int terminal_grouped(const int64_t *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
-                            const int64_t *seg_off_d, int64_t n_seg, int64_t n, int64_t delay_ns,
-                            const int64_t *window_ns, int32_t n_windows, int32_t runs, int32_t *nb_d, double *risk_d,
-                            int64_t *rec_d, int32_t *scratch_d, void *stream, bool compact = false,
-                            const int32_t *nflag_d = nullptr) {
+extern "C" int fdx_terminal_windows_grouped(const void *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
+                                            const int64_t *seg_off_d, int64_t n_seg, int64_t n, int64_t delay_ns,
+                                            const int64_t *window_ns, int32_t n_windows, int32_t flags, int32_t *nb_d,
+                                            double *risk_d, int64_t *rec_d, int32_t *scratch_d,
+                                            const int32_t *narrow_flag_d, void *stream) {
     WinArgs wa;
     int rc = check_windows(window_ns, n_windows, &wa);
     if (rc) return rc;
+    FDX_REQUIRE((flags & ~(FDX_TERM_RUNS | FDX_TERM_COMPACT)) == 0, "flags: FDX_TERM_RUNS | FDX_TERM_COMPACT only");
+    const bool runs = (flags & FDX_TERM_RUNS) != 0, compact = (flags & FDX_TERM_COMPACT) != 0;
     FDX_REQUIRE(delay_ns > 0, "delay must be > 0 ns");
     FDX_REQUIRE(n_seg >= 0 && n >= 0, "negative size");
     if (n_seg == 0 || n == 0) return FDX_OK;
@@ -1905,44 +1907,18 @@ static int terminal_grouped(const int64_t *gts_d, const uint8_t *gfraud_d, const
     FDX_REQUIRE(gfraud_d || rows_d, "fraud comes from gfraud_d or bit 31 of rows_d");
     FDX_REQUIRE(rec_d || (nb_d && risk_d), "no output");
     FDX_REQUIRE(!compact || (rec_d && n_windows == 3 && ((uintptr_t)rec_d & 15) == 0),
-                "compact records: W = 3, a 16-byte aligned record array");
-    if (nflag_d) {
-        FDX_REQUIRE(!runs && compact && n_windows == 3, "narrow payloads: compact records of single-run segments");
-        FDX_REQUIRE(delay_ns % kNsPerSec == 0, "narrow payloads need a whole-second delay");
+                "FDX_TERM_COMPACT: n_windows = 3 and a 16-byte aligned rec_d");
+    if (narrow_flag_d) {
+        FDX_REQUIRE(!runs && compact && n_windows == 3,
+                    "narrow_flag_d: flags = FDX_TERM_COMPACT (compact records of single-run segments), n_windows = 3");
+        FDX_REQUIRE(delay_ns % kNsPerSec == 0, "narrow_flag_d needs a whole-second delay_ns");
         for (int i = 0; i < n_windows; ++i)
-            FDX_REQUIRE(window_ns[i] % kNsPerSec == 0, "narrow payloads need whole-second windows (window %d)", i);
+            FDX_REQUIRE(window_ns[i] % kNsPerSec == 0, "narrow_flag_d needs whole-second windows (window_ns[%d])", i);
     }
-    terminal_launch(runs != 0, gts_d, gfraud_d, rows_d, seg_off_d, n_seg, n, delay_ns, wa, n_windows, nb_d, risk_d,
-                    rec_d, scratch_d, as_stream(stream), compact ? n : 0, nflag_d);
+    terminal_launch(runs, reinterpret_cast<const int64_t *>(gts_d), gfraud_d, rows_d, seg_off_d, n_seg, n, delay_ns, wa,
+                    n_windows, nb_d, risk_d, rec_d, scratch_d, as_stream(stream), compact ? n : 0, narrow_flag_d);
     FDX_LAUNCHED("k_terminal_g");
     return FDX_OK;
-}
-
-extern "C" int fdx_terminal_windows_grouped(const int64_t *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
-                                            const int64_t *seg_off_d, int64_t n_seg, int64_t n, int64_t delay_ns,
-                                            const int64_t *window_ns, int32_t n_windows, int32_t runs, int32_t *nb_d,
-                                            double *risk_d, int64_t *rec_d, int32_t *scratch_d, void *stream) {
-    return terminal_grouped(gts_d, gfraud_d, rows_d, seg_off_d, n_seg, n, delay_ns, window_ns, n_windows, runs, nb_d,
-                            risk_d, rec_d, scratch_d, stream);
-}
-
-extern "C" int fdx_terminal_windows_grouped_compact(const int64_t *gts_d, const uint8_t *gfraud_d,
-                                                    const int32_t *rows_d, const int64_t *seg_off_d, int64_t n_seg,
-                                                    int64_t n, int64_t delay_ns, const int64_t *window_ns,
-                                                    int32_t n_windows, int32_t runs, int64_t *rec_d,
-                                                    int32_t *scratch_d, void *stream) {
-    return terminal_grouped(gts_d, gfraud_d, rows_d, seg_off_d, n_seg, n, delay_ns, window_ns, n_windows, runs,
-                            nullptr, nullptr, rec_d, scratch_d, stream, true);
-}
-
-extern "C" int fdx_terminal_windows_grouped_narrow(const void *gts_d, const uint8_t *gfraud_d, const int32_t *rows_d,
-                                                   const int64_t *seg_off_d, int64_t n_seg, int64_t n,
-                                                   int64_t delay_ns, const int64_t *window_ns, int32_t n_windows,
-                                                   int64_t *rec_d, int32_t *scratch_d,
-                                                   const int32_t *narrow_flag_d, void *stream) {
-    FDX_REQUIRE(narrow_flag_d, "null narrow_flag_d");
-    return terminal_grouped(reinterpret_cast<const int64_t *>(gts_d), gfraud_d, rows_d, seg_off_d, n_seg, n, delay_ns,
-                            window_ns, n_windows, 0, nullptr, nullptr, rec_d, scratch_d, stream, true, narrow_flag_d);
 }
 
 extern "C" int fdx_assemble_features(int64_t n, int32_t n_windows, const double *amount_d,
@@ -2112,33 +2088,25 @@ static int customer_layout_fill(const int64_t *seg_off_d, int64_t n_seg, const i
     return FDX_OK;
 }
 
-extern "C" int fdx_customer_layout_fill_starts_grouped(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                                                       const int64_t *gts_d, const double *gamount_d,
-                                                       const int64_t *window_ns, int32_t n_windows,
-                                                       const int32_t *sorder_d, const uint32_t *goff_d,
-                                                       int64_t n_slots, int64_t *its_d, double *iamt_d,
-                                                       int32_t *irow_d, int32_t *starts_d, void *stream) {
+extern "C" int fdx_customer_layout_fill(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
+                                        const void *gts_d, const void *gamount_d, const int64_t *window_ns,
+                                        int32_t n_windows, const int32_t *sorder_d, const uint32_t *goff_d,
+                                        int64_t n_slots, int64_t *its_d, double *iamt_d, int32_t *irow_d,
+                                        int32_t *starts_d, const int32_t *narrow_flag_d, int32_t narrow_mask,
+                                        const int64_t *ts_base_d, void *stream) {
     WinArgs wa;
     int rc = check_windows(window_ns, n_windows, &wa);
     if (rc) return rc;
-    FDX_REQUIRE(starts_d, "null pointer");
-    return customer_layout_fill(seg_off_d, n_seg, cperm_d, gts_d, gamount_d, n_windows, sorder_d, goff_d, n_slots,
-                                its_d, iamt_d, irow_d, as_stream(stream), &wa, starts_d, true);
-}
-
-extern "C" int fdx_customer_layout_fill_starts_grouped_narrow(
-    const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d, const void *gts_d, const void *gamount_d,
-    const int64_t *window_ns, int32_t n_windows, const int32_t *sorder_d, const uint32_t *goff_d, int64_t n_slots,
-    int64_t *its_d, double *iamt_d, int32_t *irow_d, int32_t *starts_d, const int32_t *narrow_flag_d,
-    int32_t narrow_mask, const int64_t *ts_base_d, void *stream) {
-    WinArgs wa;
-    int rc = check_windows(window_ns, n_windows, &wa);
-    if (rc) return rc;
-    FDX_REQUIRE(starts_d && narrow_flag_d && ts_base_d, "null pointer");
-    FDX_REQUIRE(narrow_mask == FDX_NARROW_TS || narrow_mask == (FDX_NARROW_TS | FDX_NARROW_AMOUNT),
-                "narrow_mask: the re-key's, FDX_NARROW_TS or FDX_NARROW_TS | FDX_NARROW_AMOUNT");
-    for (int i = 0; i < n_windows; ++i)
-        FDX_REQUIRE(window_ns[i] % kNsPerSec == 0, "narrow payloads need whole-second windows (window %d)", i);
+    FDX_REQUIRE(starts_d, "null starts_d");
+    if (narrow_flag_d) {
+        FDX_REQUIRE(narrow_mask == FDX_NARROW_TS || narrow_mask == (FDX_NARROW_TS | FDX_NARROW_AMOUNT),
+                    "narrow_mask: the re-key's, FDX_NARROW_TS or FDX_NARROW_TS | FDX_NARROW_AMOUNT");
+        FDX_REQUIRE(ts_base_d, "null ts_base_d");
+        for (int i = 0; i < n_windows; ++i)
+            FDX_REQUIRE(window_ns[i] % kNsPerSec == 0, "narrow_flag_d needs whole-second windows (window_ns[%d])", i);
+    } else {
+        FDX_REQUIRE(narrow_mask == 0, "narrow_mask needs narrow_flag_d");
+    }
     return customer_layout_fill(seg_off_d, n_seg, cperm_d, reinterpret_cast<const int64_t *>(gts_d),
                                 reinterpret_cast<const double *>(gamount_d), n_windows, sorder_d, goff_d, n_slots,
                                 its_d, iamt_d, irow_d, as_stream(stream), &wa, starts_d, true, narrow_flag_d,
@@ -2147,73 +2115,27 @@ extern "C" int fdx_customer_layout_fill_starts_grouped_narrow(
 
 // plan + fill in one call (the slot count must fit max_slots: FDX_E_WORKSPACE with *n_slots_h
 // set otherwise)
-static int customer_layout(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                           const int64_t *ts_d, const double *amount_d, int32_t n_windows,
-                           int32_t *sorder_d, uint32_t *goff_d, int64_t *its_d, double *iamt_d,
-                           int32_t *irow_d, int64_t max_slots, int64_t *n_slots_h, void *ws,
-                           size_t ws_bytes, void *stream, const WinArgs *wa, int32_t *starts_d, bool grouped = false) {
+extern "C" int fdx_customer_layout(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
+                                   const int64_t *ts_d, const double *amount_d, const int64_t *window_ns,
+                                   int32_t n_windows, int32_t flags, int32_t *sorder_d, uint32_t *goff_d,
+                                   int64_t *its_d, double *iamt_d, int32_t *irow_d, int32_t *starts_d,
+                                   int64_t max_slots, int64_t *n_slots_h, void *ws, size_t ws_bytes, void *stream) {
+    FDX_REQUIRE((window_ns == nullptr) == (starts_d == nullptr), "window_ns and starts_d go together");
+    FDX_REQUIRE((flags & ~FDX_LAYOUT_GROUPED) == 0, "flags: FDX_LAYOUT_GROUPED only");
+    WinArgs wa;
+    int rc = window_ns ? check_windows(window_ns, n_windows, &wa) : FDX_OK;
+    if (rc) return rc;
     FDX_REQUIRE(cperm_d && ts_d && amount_d && its_d && iamt_d && irow_d, "null pointer");
-    int rc = fdx_customer_layout_plan(seg_off_d, n_seg, n_windows, sorder_d, goff_d, n_slots_h, ws, ws_bytes, stream);
+    rc = fdx_customer_layout_plan(seg_off_d, n_seg, n_windows, sorder_d, goff_d, n_slots_h, ws, ws_bytes, stream);
     if (rc) return rc;
     if (*n_slots_h > max_slots) {
         set_error("interleaved layout needs %lld slots > max_slots %lld", (long long)*n_slots_h, (long long)max_slots);
         return FDX_E_WORKSPACE;
     }
     return customer_layout_fill(seg_off_d, n_seg, cperm_d, ts_d, amount_d, n_windows, sorder_d, goff_d, *n_slots_h,
-                                its_d, iamt_d, irow_d, as_stream(stream), wa, starts_d, grouped);
+                                its_d, iamt_d, irow_d, as_stream(stream), window_ns ? &wa : nullptr, starts_d,
+                                (flags & FDX_LAYOUT_GROUPED) != 0);
 }
-
-extern "C" int fdx_customer_layout(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                                   const int64_t *ts_d, const double *amount_d, int32_t n_windows,
-                                   int32_t *sorder_d, uint32_t *goff_d, int64_t *its_d, double *iamt_d,
-                                   int32_t *irow_d, int64_t max_slots, int64_t *n_slots_h, void *ws,
-                                   size_t ws_bytes, void *stream) {
-    return customer_layout(seg_off_d, n_seg, cperm_d, ts_d, amount_d, n_windows, sorder_d, goff_d, its_d, iamt_d,
-                           irow_d, max_slots, n_slots_h, ws, ws_bytes, stream, nullptr, nullptr);
-}
-
-extern "C" int fdx_customer_layout_starts(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                                          const int64_t *ts_d, const double *amount_d, const int64_t *window_ns,
-                                          int32_t n_windows, int32_t *sorder_d, uint32_t *goff_d, int64_t *its_d,
-                                          double *iamt_d, int32_t *irow_d, int32_t *starts_d, int64_t max_slots,
-                                          int64_t *n_slots_h, void *ws, size_t ws_bytes, void *stream) {
-    WinArgs wa;
-    int rc = check_windows(window_ns, n_windows, &wa);
-    if (rc) return rc;
-    FDX_REQUIRE(starts_d, "null pointer");
-    return customer_layout(seg_off_d, n_seg, cperm_d, ts_d, amount_d, n_windows, sorder_d, goff_d, its_d, iamt_d,
-                           irow_d, max_slots, n_slots_h, ws, ws_bytes, stream, &wa, starts_d);
-}
-
-extern "C" int fdx_customer_layout_starts_grouped(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                                                  const int64_t *gts_d, const double *gamount_d,
-                                                  const int64_t *window_ns, int32_t n_windows, int32_t *sorder_d,
-                                                  uint32_t *goff_d, int64_t *its_d, double *iamt_d, int32_t *irow_d,
-                                                  int32_t *starts_d, int64_t max_slots, int64_t *n_slots_h, void *ws,
-                                                  size_t ws_bytes, void *stream) {
-    WinArgs wa;
-    int rc = check_windows(window_ns, n_windows, &wa);
-    if (rc) return rc;
-    FDX_REQUIRE(starts_d, "null pointer");
-    return customer_layout(seg_off_d, n_seg, cperm_d, gts_d, gamount_d, n_windows, sorder_d, goff_d, its_d, iamt_d,
-                           irow_d, max_slots, n_slots_h, ws, ws_bytes, stream, &wa, starts_d, true);
-}
-
-extern "C" int fdx_customer_layout_grouped(const int64_t *seg_off_d, int64_t n_seg, const int32_t *cperm_d,
-                                           const int64_t *gts_d, const double *gamount_d, int32_t n_windows,
-                                           int32_t *sorder_d, uint32_t *goff_d, int64_t *its_d, double *iamt_d,
-                                           int32_t *irow_d, int64_t max_slots, int64_t *n_slots_h, void *ws,
-                                           size_t ws_bytes, void *stream) {
-    return customer_layout(seg_off_d, n_seg, cperm_d, gts_d, gamount_d, n_windows, sorder_d, goff_d, its_d, iamt_d,
-                           irow_d, max_slots, n_slots_h, ws, ws_bytes, stream, nullptr, nullptr, true);
-}
-
-/* slot form of the scan mode over a layout built WITH window starts (fdx.h) */
-extern "C" int fdx_customer_windows_scan_slots(const double *gamount_d, const int64_t *seg_off_d, int64_t n_seg,
-                                               int64_t n, const int32_t *sorder_d, const uint32_t *goff_d,
-                                               int64_t n_slots, int32_t n_windows, const int32_t *starts_d,
-                                               int32_t *nb_d, double *sum_d, void *ws, size_t ws_bytes,
-                                               void *stream);
 
 extern "C" size_t fdx_customer_windows_scan_workspace_size(int64_t n, int64_t n_seg) {
     if (n < 0 || n_seg < 0) return 0;

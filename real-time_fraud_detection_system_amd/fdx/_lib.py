@@ -16,8 +16,10 @@ FDX_OK = 0
 FDX_E_UNSUPPORTED = -3
 FDX_FLAGS_NOTEBOOK = 0
 FDX_FLAGS_SPARK = 1
-FDX_NARROW_TS, FDX_NARROW_AMOUNT = 1, 2  # fdx_rekey_payload_narrow's narrow_mask
-FDX_ROWS_INPUT_ORDER = 1  # fdx_forest_prepare_grouped_rows: the featurized table by input row
+FDX_NARROW_TS, FDX_NARROW_AMOUNT = 1, 2  # fdx_rekey_payload_opts.narrow_mask
+FDX_LAYOUT_GROUPED = 1  # fdx_customer_layout's flags
+FDX_TERM_RUNS, FDX_TERM_COMPACT = 1, 2  # fdx_terminal_windows_grouped's flags
+FDX_ROWS_INPUT_ORDER = 1  # fdx_forest_prepare_grouped: the featurized table by input row
 FDX_ROWS_SLOT_ORDER = 2   # ... by scoring slot (coalesced; each record carries its row)
 FDX_KEY_MOD, FDX_KEY_DIV, FDX_KEY_SUB = 0, 1, 2
 FDX_SELECT_LATEST, FDX_SELECT_FIRST_IN_RANGE = 0, 1  # fdx_table_select
@@ -56,6 +58,12 @@ class SynthDesc(ctypes.Structure):
     ]
 
 
+class RekeyPayloadOpts(ctypes.Structure):
+    """fdx_rekey_payload_opts (include/fdx.h)"""
+    _fields_ = [("bad_d", P), ("sorted_keys_d", P), ("hist0_d", P), ("hist0_bytes", c_sz), ("narrow_flag_d", P),
+                ("narrow_mask", c_i32)]
+
+
 # name -> (restype, argtypes); exactly the symbols declared in include/fdx.h
 SIGNATURES = {
     "fdx_last_error": (ctypes.c_char_p, []),
@@ -66,9 +74,7 @@ SIGNATURES = {
     "fdx_terminal_windows": (ctypes.c_int, [P, P, P, c_i64, c_i64, c_i64, P, c_i32, P, P, P, c_sz, P]),
     "fdx_assemble_features": (ctypes.c_int, [c_i64, c_i32, P, P, P, P, P, P, P, P, P, P, c_i64, P]),
     "fdx_customer_layout_workspace_size": (c_sz, [c_i64]),
-    "fdx_customer_layout": (ctypes.c_int, [P, c_i64, P, P, P, c_i32, P, P, P, P, P, c_i64, P, P, c_sz, P]),
-    "fdx_customer_layout_starts": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i32, P, P, P, P, P, P, c_i64, P, P, c_sz,
-                                                  P]),
+    "fdx_customer_layout": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i32, c_i32, P, P, P, P, P, P, c_i64, P, P, c_sz, P]),
     "fdx_customer_windows_walk": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i32, P, P, P, P]),
     "fdx_customer_windows_interleaved": (ctypes.c_int, [P, P, P, P, P, c_i64, c_i64, P, c_i32, P, P, P]),
     "fdx_exclusive_scan_u32_workspace_size": (c_sz, [c_i64]),
@@ -77,8 +83,7 @@ SIGNATURES = {
     "fdx_key_segments": (ctypes.c_int, [P, c_i64, c_i64, P, P, P, c_sz, P]),
     "fdx_customer_layout_plan": (ctypes.c_int, [P, c_i64, c_i32, P, P, P, P, c_sz, P]),
     "fdx_customer_layout_plan_async": (ctypes.c_int, [P, c_i64, c_i32, P, P, P, P, c_sz, P]),
-    "fdx_customer_layout_fill_starts_grouped": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i32, P, P, c_i64, P, P, P, P,
-                                                                P]),
+    "fdx_customer_layout_fill": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i32, P, P, c_i64, P, P, P, P, P, c_i32, P, P]),
     "fdx_segment_latest": (ctypes.c_int, [P, P, P, c_i64, P, P]),
     "fdx_segment_first_in_range": (ctypes.c_int, [P, P, P, c_i64, c_i64, c_i64, P, P]),
     "fdx_table_select_workspace_size": (c_sz, [c_i64]),
@@ -104,25 +109,14 @@ SIGNATURES = {
     "fdx_rekey_workspace_size": (c_sz, [c_i64, c_i32]),
     "fdx_rekey": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, c_sz, P]),
     "fdx_rekey_payload_workspace_size": (c_sz, [c_i64, c_i32, c_i32]),
-    "fdx_rekey_payload": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, c_sz, P]),
-    "fdx_rekey_payload_checked": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, P, c_sz, P]),
-    "fdx_rekey_payload_keys": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, P, c_sz, P]),
+    "fdx_rekey_payload": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, P, P, P,
+                                         ctypes.POINTER(RekeyPayloadOpts), P, c_sz, P]),
     "fdx_segment_offsets_sorted": (ctypes.c_int, [P, c_i64, c_i64, P, P]),
     "fdx_rekey_hist0_size": (c_sz, [c_i64, c_i32]),
     "fdx_rekey_hist0": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, c_sz, P, P]),
-    "fdx_rekey_payload_hist0": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, P, c_sz, P]),
-    "fdx_rekey_payload_narrow": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, P, P, c_i32, P, c_sz,
-                                                P]),
     "fdx_narrow_windows_ok": (ctypes.c_int, [P, c_i32, c_i64]),
-    "fdx_customer_layout_fill_starts_grouped_narrow": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i32, P, P, c_i64, P, P,
-                                                                       P, P, P, c_i32, P, P]),
-    "fdx_terminal_windows_grouped_narrow": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i64, P, c_i32, P, P, P, P]),
-    "fdx_terminal_windows_grouped": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i64, P, c_i32, c_i32, P, P, P, P, P]),
-    "fdx_terminal_windows_grouped_compact": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i64, P, c_i32, c_i32, P, P,
-                                                            P]),
-    "fdx_customer_layout_starts_grouped": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i32, P, P, P, P, P, P, c_i64, P, P,
-                                                          c_sz, P]),
-    "fdx_customer_layout_grouped": (ctypes.c_int, [P, c_i64, P, P, P, c_i32, P, P, P, P, P, c_i64, P, P, c_sz, P]),
+    "fdx_terminal_windows_grouped": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i64, P, c_i32, c_i32, P, P, P, P, P,
+                                                    P]),
     "fdx_customer_windows_scan_workspace_size": (c_sz, [c_i64, c_i64]),
     "fdx_customer_windows_scan": (ctypes.c_int, [P, P, P, c_i64, c_i64, P, c_i32, P, P, c_i64, P, P, c_i32, P, c_sz,
                                                  P]),
@@ -161,9 +155,8 @@ SIGNATURES = {
     "fdx_forest_traverse": (ctypes.c_int, [P, c_i64, P, P, P, c_sz, P]),
     "fdx_forest_prepare_features": (ctypes.c_int, [P, c_i64, c_i32, P, P, P, P, P, P, P, P, P, P, c_sz, P]),
     "fdx_forest_clear_flag": (ctypes.c_int, [P, c_i64, P, c_sz, P]),
-    "fdx_forest_prepare_grouped": (ctypes.c_int, [P, c_i64, c_i32, c_i32, c_i32, P, P, P, P, P, P, P, P, c_sz, P]),
-    "fdx_forest_prepare_grouped_rows": (ctypes.c_int, [P, c_i64, c_i32, c_i32, c_i32, P, P, P, P, P, P, P, P, c_i64,
-                                                       c_i32, P, c_sz, P]),
+    "fdx_forest_prepare_grouped": (ctypes.c_int, [P, c_i64, c_i32, c_i32, c_i32, P, P, P, P, P, P, P, P, c_i64, c_i32,
+                                                  P, c_sz, P]),
     "fdx_forest_traverse_perm": (ctypes.c_int, [P, c_i64, P, P, P, P, c_sz, P]),
     "fdx_forest_set_variant": (ctypes.c_int, [P, c_i32]),
     "fdx_forest_get_variant": (ctypes.c_int, [P, P]),
@@ -186,7 +179,7 @@ def load():
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
-        if L.fdx_abi_version() != 2:
+        if L.fdx_abi_version() != 3:
             raise FdxError("libfdx ABI version mismatch")
         _lib = L
     return _lib

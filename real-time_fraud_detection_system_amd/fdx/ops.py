@@ -129,17 +129,17 @@ def rekey_payload(keys: torch.Tensor, n_keys: int, pay0: torch.Tensor | None = N
     """rekey that also moves up to two 8-byte columns (int64 / float64, input row order) into
     grouped order inside the radix passes; flag (uint8 per row) is packed into bit 31 of perm.
     bad (int32 device scalar): receives the number of keys outside [0, n_keys), counted in the
-    first radix pass (fdx_rekey_payload_checked; see KeyRangeCheck.from_count).
+    first radix pass (see KeyRangeCheck.from_count).
     keys_out (int32 [n], 16-byte aligned): receives the sorted keys instead of seg_off being
-    derived (fdx_rekey_payload_keys; segment_offsets_sorted derives it later, so that another
-    re-key sharing the scratch may start in between).  hist0: the first pass's table from
-    rekey_hist0 over the same keys (fdx_rekey_payload_hist0; the id-range count was taken there,
-    so bad must be None).
+    derived (segment_offsets_sorted derives it later, so that another re-key sharing the scratch
+    may start in between).  hist0: the first pass's table from rekey_hist0 over the same keys (the
+    id-range count was taken there, so bad must be None).  One C call, fdx_rekey_payload: these
+    are its fdx_rekey_payload_opts, and it refuses the combinations fdx.h rules out.
     -> (perm int32, seg_off int64[n_keys+1] (None with seg_off=False or keys_out), pay0 grouped |
     None, pay1 grouped | None).  alloc: see Arena (outputs "perm", "seg", "pay0", "pay1", scratch
     "rekey_ws").
-    narrow (not None): fdx_rekey_payload_narrow -- pay0 is the int64 timestamps, pay1 (optional) the
-    float64 amounts, and they travel as int32 seconds / int32 cents when every value has that form
+    narrow (not None): the narrow form (no keys_out) -- pay0 is the int64 timestamps, pay1 (optional)
+    the float64 amounts, and they travel as int32 seconds / int32 cents when every value has that form
     exactly (decided on the device, no host sync).  A fifth output, a Narrow (the int32 [1] device
     flag + the mask that was tried), says which form the grouped columns hold (flag 0: the 4-byte
     forms in the first 4 n bytes of each column of the mask; else the 8-byte columns); hand it to
@@ -167,49 +167,29 @@ def rekey_payload(keys: torch.Tensor, n_keys: int, pay0: torch.Tensor | None = N
     L = _lib.load()
     ws = A("rekey_ws", max(L.fdx_rekey_payload_workspace_size(n, kb, (pay0 is not None) + (pay1 is not None)), 1),
            torch.uint8)
-    if narrow is not None:
-        if keys_out is not None or pay0 is None or pay0.dtype != torch.int64 or \
-                (pay1 is not None and pay1.dtype != torch.float64):
-            raise FdxError("narrow: pay0 = int64 timestamps, pay1 = float64 amounts or None, no keys_out")
-        if hist0 is not None and (bad is not None or hist0.numel() < L.fdx_rekey_hist0_size(n, kb)):
-            raise FdxError("hist0 takes no bad (counted by rekey_hist0) and must hold fdx_rekey_hist0_size bytes")
-        if bad is not None:
-            _dev(bad, torch.int32, "bad")
-        mask = (_lib.FDX_NARROW_TS | _lib.FDX_NARROW_AMOUNT) if narrow is True else int(narrow)
-        if pay1 is None:
-            mask &= _lib.FDX_NARROW_TS
-        nflag = A("nflag", 1, torch.int32)
-        check(L.fdx_rekey_payload_narrow(_ptr(keys), n, kb, int(n_keys), _ptr(flag), _ptr(pay0), _ptr(pay1), _ptr(perm),
-                                         _ptr(seg), _ptr(o0), _ptr(o1), _ptr(bad), _ptr(hist0), _ptr(nflag),
-                                         mask, _ptr(ws), ws.numel(), _s(stream)),
-              "fdx_rekey_payload_narrow")
-        return perm, seg, o0, o1, Narrow(nflag, mask)
-    if hist0 is not None:
-        if bad is not None or keys_out is not None:
-            raise FdxError("hist0 takes neither bad (counted by rekey_hist0) nor keys_out")
-        if hist0.numel() < L.fdx_rekey_hist0_size(n, kb):
-            raise FdxError("hist0 is smaller than fdx_rekey_hist0_size")
-        check(L.fdx_rekey_payload_hist0(_ptr(keys), n, kb, int(n_keys), _ptr(flag), _ptr(pay0), _ptr(pay1), _ptr(perm),
-                                        _ptr(seg), _ptr(o0), _ptr(o1), _ptr(hist0), _ptr(ws), ws.numel(), _s(stream)),
-              "fdx_rekey_payload_hist0")
-    elif keys_out is not None:
+    if bad is not None:
+        _dev(bad, torch.int32, "bad")
+    if keys_out is not None:
         _dev(keys_out, torch.int32, "keys_out")
         if keys_out.numel() < n:
             raise FdxError(f"keys_out holds {keys_out.numel()} keys, {n} needed")
-        if bad is not None:
-            _dev(bad, torch.int32, "bad")
-        check(L.fdx_rekey_payload_keys(_ptr(keys), n, kb, int(n_keys), _ptr(flag), _ptr(pay0), _ptr(pay1), _ptr(perm),
-                                       _ptr(keys_out), _ptr(o0), _ptr(o1), _ptr(bad), _ptr(ws), ws.numel(), _s(stream)),
-              "fdx_rekey_payload_keys")
-    elif bad is not None:
-        _dev(bad, torch.int32, "bad")
-        check(L.fdx_rekey_payload_checked(_ptr(keys), n, kb, int(n_keys), _ptr(flag), _ptr(pay0), _ptr(pay1),
-                                          _ptr(perm), _ptr(seg), _ptr(o0), _ptr(o1), _ptr(bad), _ptr(ws), ws.numel(),
-                                          _s(stream)), "fdx_rekey_payload_checked")
-    else:
-        check(L.fdx_rekey_payload(_ptr(keys), n, kb, int(n_keys), _ptr(flag), _ptr(pay0), _ptr(pay1), _ptr(perm),
-                                  _ptr(seg), _ptr(o0), _ptr(o1), _ptr(ws), ws.numel(), _s(stream)), "fdx_rekey_payload")
-    return perm, seg, o0, o1
+    if hist0 is not None and keys_out is not None:
+        raise FdxError("hist0 does not take keys_out")
+    opts = _lib.RekeyPayloadOpts(bad_d=_ptr(bad), sorted_keys_d=_ptr(keys_out), hist0_d=_ptr(hist0),
+                                 hist0_bytes=0 if hist0 is None else hist0.numel())
+    nar = None
+    if narrow is not None:
+        if pay0 is None or pay0.dtype != torch.int64 or (pay1 is not None and pay1.dtype != torch.float64):
+            raise FdxError("narrow: pay0 = int64 timestamps, pay1 = float64 amounts or None")
+        mask = (_lib.FDX_NARROW_TS | _lib.FDX_NARROW_AMOUNT) if narrow is True else int(narrow)
+        if pay1 is None:
+            mask &= _lib.FDX_NARROW_TS
+        nar = Narrow(A("nflag", 1, torch.int32), mask)
+        opts.narrow_flag_d, opts.narrow_mask = _ptr(nar.flag), mask
+    check(L.fdx_rekey_payload(_ptr(keys), n, kb, int(n_keys), _ptr(flag), _ptr(pay0), _ptr(pay1), _ptr(perm), _ptr(seg),
+                              _ptr(o0), _ptr(o1), ctypes.byref(opts), _ptr(ws), ws.numel(), _s(stream)),
+          "fdx_rekey_payload")
+    return (perm, seg, o0, o1) if nar is None else (perm, seg, o0, o1, nar)
 
 
 def narrow_windows_ok(windows_ns: Sequence[int], delay_ns: int = 0) -> bool:
@@ -491,21 +471,16 @@ def customer_layout(seg_off, cperm, ts_ns, amount, n_windows: int, stream=None, 
         iamt = torch.empty(max_slots, dtype=torch.float64, device=dev)
         irow = torch.empty(max_slots, dtype=torch.int32, device=dev)
         ns = ctypes.c_int64(0)
-        if windows_days is None:
-            starts = None
-            fn = L.fdx_customer_layout_grouped if grouped else L.fdx_customer_layout
-            rc = fn(_ptr(seg_off), n_seg, _ptr(cperm), _ptr(ts_ns), _ptr(amount), int(n_windows),
-                    _ptr(sorder), _ptr(goff), _ptr(its), _ptr(iamt), _ptr(irow), max_slots,
-                    ctypes.byref(ns), _ptr(ws), ws.numel(), _s(stream))
-        else:
+        starts = None
+        if windows_days is not None:
             if len(windows_days) != int(n_windows):
                 raise FdxError("windows_days must have n_windows entries")
             starts = torch.empty(int(n_windows) * max_slots, dtype=torch.int32, device=dev)
-            fn = L.fdx_customer_layout_starts_grouped if grouped else L.fdx_customer_layout_starts
-            rc = fn(_ptr(seg_off), n_seg, _ptr(cperm), _ptr(ts_ns), _ptr(amount),
-                                              _win_ns(windows_days), int(n_windows), _ptr(sorder), _ptr(goff),
-                                              _ptr(its), _ptr(iamt), _ptr(irow), _ptr(starts), max_slots,
-                                              ctypes.byref(ns), _ptr(ws), ws.numel(), _s(stream))
+        rc = L.fdx_customer_layout(_ptr(seg_off), n_seg, _ptr(cperm), _ptr(ts_ns), _ptr(amount),
+                                   None if windows_days is None else _win_ns(windows_days), int(n_windows),
+                                   _lib.FDX_LAYOUT_GROUPED if grouped else 0, _ptr(sorder), _ptr(goff), _ptr(its),
+                                   _ptr(iamt), _ptr(irow), _ptr(starts), max_slots, ctypes.byref(ns), _ptr(ws),
+                                   ws.numel(), _s(stream))
         if rc == -4 and ns.value > max_slots:
             if ns.value > S * n:  # every group pads to its longest segment: <= S slots per row
                 raise FdxError(f"customer layout: {ns.value} slots for {n} rows -- inconsistent segment "
@@ -630,17 +605,14 @@ def customer_layout_fill(plan: LayoutPlan, seg_off, cperm, gts, gamt, windows_da
     iamt = A("iamt", m, torch.float64)
     irow = A("irow", m, torch.int32)
     starts = A("starts", W * m, torch.int32)
-    if m and narrow is not None and narrow.mask:
-        _dev(ts_base, torch.int64, "ts_base")
-        check(_lib.load().fdx_customer_layout_fill_starts_grouped_narrow(
+    if m:
+        nflag, mask = (narrow.flag, narrow.mask) if narrow is not None and narrow.mask else (None, 0)
+        if nflag is not None:
+            _dev(ts_base, torch.int64, "ts_base")
+        check(_lib.load().fdx_customer_layout_fill(
             _ptr(seg_off), seg_off.numel() - 1, _ptr(cperm), _ptr(gts), _ptr(gamt), _win_ns(windows_days), W,
-            _ptr(plan.sorder), _ptr(plan.goff), m, _ptr(its), _ptr(iamt), _ptr(irow), _ptr(starts),
-            _ptr(narrow.flag), narrow.mask, _ptr(ts_base), _s(stream)), "fdx_customer_layout_fill_starts_grouped_narrow")
-    elif m:
-        check(_lib.load().fdx_customer_layout_fill_starts_grouped(
-            _ptr(seg_off), seg_off.numel() - 1, _ptr(cperm), _ptr(gts), _ptr(gamt), _win_ns(windows_days), W,
-            _ptr(plan.sorder), _ptr(plan.goff), m, _ptr(its), _ptr(iamt), _ptr(irow), _ptr(starts), _s(stream)),
-            "fdx_customer_layout_fill_starts_grouped")
+            _ptr(plan.sorder), _ptr(plan.goff), m, _ptr(its), _ptr(iamt), _ptr(irow), _ptr(starts), _ptr(nflag), mask,
+            _ptr(ts_base) if mask else None, _s(stream)), "fdx_customer_layout_fill")
     return CustomerLayout(plan.sorder, plan.goff, its, iamt, irow, m, starts, tuple(windows_days))
 
 
@@ -681,9 +653,9 @@ def terminal_windows_compact(gts, seg_off, rows=None, gfraud=None, delay_days=7,
                              runs: bool = False, stream=None, alloc=None, narrow: Narrow | None = None):
     """terminal_windows_grouped's count records by row in the COMPACT format (3 windows): an
     int64 [5 n] array, row r's 16-byte record at words [2 r, 2 r + 2), the overflow area
-    [2 n, 5 n) (fdx.h fdx_terminal_windows_grouped_compact).  compact_records_unpack turns it
-    into the [n, 3] records (alloc: see Arena).  narrow: rekey_payload(narrow=...)'s fifth output
-    -- gts holds the form it names (fdx_terminal_windows_grouped_narrow)."""
+    [2 n, 5 n) (fdx.h FDX_TERM_COMPACT).  compact_records_unpack turns it into the [n, 3] records
+    (alloc: see Arena).  narrow: rekey_payload(narrow=...)'s fifth output -- gts holds the form it
+    names (single-run segments only)."""
     _dev(gts, torch.int64, "gts"); _dev(seg_off, torch.int64, "seg_off")
     if rows is not None:
         _dev(rows, torch.int32, "rows")
@@ -697,20 +669,13 @@ def terminal_windows_compact(gts, seg_off, rows=None, gfraud=None, delay_days=7,
     A = alloc or _fresh(gts.device)
     rec = A("rec", max(5 * n, 2), torch.int64)  # 256-byte aligned
     scratch = A("scratch", max(n, 1), torch.int32)
-    if narrow is not None and narrow.mask:
-        if runs:
-            raise FdxError("narrow: single-run segments only")
-        check(_lib.load().fdx_terminal_windows_grouped_narrow(_ptr(gts), _ptr(gfraud), _ptr(rows), _ptr(seg_off),
-                                                              seg_off.numel() - 1, n, int(delay_days) * NS_PER_DAY,
-                                                              _win_ns(windows_days), 3, _ptr(rec), _ptr(scratch),
-                                                              _ptr(narrow.flag), _s(stream)),
-              "fdx_terminal_windows_grouped_narrow")
-        return rec
-    check(_lib.load().fdx_terminal_windows_grouped_compact(_ptr(gts), _ptr(gfraud), _ptr(rows), _ptr(seg_off),
-                                                           seg_off.numel() - 1, n, int(delay_days) * NS_PER_DAY,
-                                                           _win_ns(windows_days), 3, int(bool(runs)), _ptr(rec),
-                                                           _ptr(scratch), _s(stream)),
-          "fdx_terminal_windows_grouped_compact")
+    nflag = narrow.flag if narrow is not None and narrow.mask else None
+    check(_lib.load().fdx_terminal_windows_grouped(_ptr(gts), _ptr(gfraud), _ptr(rows), _ptr(seg_off),
+                                                   seg_off.numel() - 1, n, int(delay_days) * NS_PER_DAY,
+                                                   _win_ns(windows_days), 3,
+                                                   _lib.FDX_TERM_COMPACT | (_lib.FDX_TERM_RUNS if runs else 0), None,
+                                                   None, _ptr(rec), _ptr(scratch), _ptr(nflag), _s(stream)),
+          "fdx_terminal_windows_grouped")
     return rec
 
 
@@ -733,15 +698,15 @@ def terminal_windows_grouped(gts, seg_off, rows=None, gfraud=None, delay_days=7,
     scratch = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     L = _lib.load()
     args = (_ptr(gts), _ptr(gfraud), _ptr(rows), _ptr(seg_off), seg_off.numel() - 1, n, int(delay_days) * NS_PER_DAY,
-            _win_ns(windows_days), W, int(bool(runs)))
+            _win_ns(windows_days), W, _lib.FDX_TERM_RUNS if runs else 0)
     if records:
         rec = torch.empty((n, W), dtype=torch.int64, device=dev)
-        check(L.fdx_terminal_windows_grouped(*args, None, None, _ptr(rec), _ptr(scratch), _s(stream)),
+        check(L.fdx_terminal_windows_grouped(*args, None, None, _ptr(rec), _ptr(scratch), None, _s(stream)),
               "fdx_terminal_windows_grouped")
         return rec
     nb = torch.empty((W, n), dtype=torch.int32, device=dev)
     risk = torch.empty((W, n), dtype=torch.float64, device=dev)
-    check(L.fdx_terminal_windows_grouped(*args, _ptr(nb), _ptr(risk), None, _ptr(scratch), _s(stream)),
+    check(L.fdx_terminal_windows_grouped(*args, _ptr(nb), _ptr(risk), None, _ptr(scratch), None, _s(stream)),
           "fdx_terminal_windows_grouped")
     return nb, risk
 
@@ -909,11 +874,10 @@ def forest_prepare_grouped(forest: "Forest", flags_mode: int, cts, camt, cnb, ca
         if isinstance(rows_out, FeatureTable) and rows_out.cap < n:
             raise ValueError(f"the feature table holds {rows_out.cap} slots < {n}")
         out, cap, order = rows_out.buf, rows_out.cap, rows_out.order
-    check(_lib.load().fdx_forest_prepare_grouped_rows(forest._h, n, W, int(flags_mode), opts, _ptr(cts),
-                                                      _ptr(camt), _ptr(cnb),
-                                                      _ptr(cavg), _ptr(cperm), _ptr(term_inv), _ptr(term_rec),
-                                                      _ptr(out), cap, order, _ptr(ws), ws.numel(), _s(stream)),
-          "fdx_forest_prepare_grouped_rows")
+    check(_lib.load().fdx_forest_prepare_grouped(forest._h, n, W, int(flags_mode), opts, _ptr(cts), _ptr(camt),
+                                                 _ptr(cnb), _ptr(cavg), _ptr(cperm), _ptr(term_inv), _ptr(term_rec),
+                                                 _ptr(out), cap, order, _ptr(ws), ws.numel(), _s(stream)),
+          "fdx_forest_prepare_grouped")
 
 
 class FeatureRecords:

@@ -226,7 +226,7 @@ class FraudPipeline:
                 th0 = None
                 # the terminal re-key's first histogram pass (+ scan, + the terminal id-range count) on
                 # the side stream at the step's start, beside the customer re-key, instead of after it
-                # on the critical chain (fdx_rekey_hist0 / fdx_rekey_payload_hist0)
+                # on the critical chain (fdx_rekey_hist0 / fdx_rekey_payload's hist0_d)
                 # (overlapped mode only: on one stream it would just run first, and the per-stage
                 # times bench.py takes in that mode would book it to the customer re-key)
                 if overlap:

@@ -32,7 +32,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared_functions():
         assert hasattr(L, name), name
     assert set(_lib.SIGNATURES) == set(declared_functions())
-    assert L.fdx_abi_version() == 2
+    assert L.fdx_abi_version() == 3
 
 
 def test_error_path_without_gpu():
@@ -43,6 +43,67 @@ def test_error_path_without_gpu():
     assert rc == -1
     assert b"window" in L.fdx_last_error()
     assert L.fdx_rekey_workspace_size(1000, 16) > 0
+
+
+def test_merged_entry_points_refuse_what_the_header_rules_out():
+    """fdx_rekey_payload, fdx_customer_layout, fdx_customer_layout_fill and
+    fdx_terminal_windows_grouped: every combination of options include/fdx.h rules out is
+    FDX_E_INVALID with the offending argument named -- before any HIP call, so dummy pointers do."""
+    from fdx import _lib
+
+    L = _lib.load()
+    P, Q = ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1004)  # never dereferenced; Q is not 16-byte aligned
+    n, kb, n_keys = 3 * 4096 + 17, 9, 300
+    hb = L.fdx_rekey_hist0_size(n, kb)
+    assert hb > 0
+    O = _lib.RekeyPayloadOpts
+    both = _lib.FDX_NARROW_TS | _lib.FDX_NARROW_AMOUNT
+
+    def rekey(opts, pay0=P):
+        return L.fdx_rekey_payload(P, n, kb, n_keys, None, pay0, None, P, P, pay0, None, ctypes.byref(opts), P, 1 << 40,
+                                   None)
+
+    W3 = (ctypes.c_int64 * 3)(86_400 * 10**9, 7 * 86_400 * 10**9, 30 * 86_400 * 10**9)
+    Wfrac = (ctypes.c_int64 * 3)(10**9, 1_500_000_000, 2 * 10**9)
+
+    def layout(window_ns, starts):
+        return L.fdx_customer_layout(P, 10, P, P, P, window_ns, 3, 0, P, P, P, P, P, starts, 100, P, P, 1 << 40, None)
+
+    def fill(nflag, mask, ts_base=P, window_ns=W3):
+        return L.fdx_customer_layout_fill(P, 10, P, P, P, window_ns, 3, P, P, 100, P, P, P, P, nflag, mask, ts_base,
+                                          None)
+
+    def terminal(flags, n_windows=3, delay=10**9, window_ns=W3):
+        return L.fdx_terminal_windows_grouped(P, None, P, P, 1, 8, delay, window_ns, n_windows, flags, None, None, P, P,
+                                              P, None)
+
+    cases = [
+        (lambda: rekey(O(bad_d=P, hist0_d=P, hist0_bytes=hb)), b"bad_d"),
+        (lambda: rekey(O(hist0_d=P, hist0_bytes=hb - 1)), b"hist0_bytes"),
+        (lambda: rekey(O(sorted_keys_d=Q)), b"sorted_keys_d"),
+        (lambda: rekey(O(narrow_flag_d=P, narrow_mask=both), pay0=None), b"pay0_d"),
+        (lambda: rekey(O(narrow_flag_d=P, narrow_mask=both, sorted_keys_d=P)), b"sorted_keys_d"),
+        (lambda: rekey(O(narrow_flag_d=P, narrow_mask=_lib.FDX_NARROW_AMOUNT)), b"narrow_mask"),
+        (lambda: rekey(O(narrow_flag_d=P, narrow_mask=4)), b"narrow_mask"),
+        (lambda: rekey(O(narrow_mask=_lib.FDX_NARROW_TS)), b"narrow_mask"),
+        (lambda: layout(W3, None), b"starts_d"),
+        (lambda: layout(None, P), b"window_ns"),
+        (lambda: fill(P, 0), b"narrow_mask"),
+        (lambda: fill(P, _lib.FDX_NARROW_AMOUNT), b"narrow_mask"),
+        (lambda: fill(None, _lib.FDX_NARROW_TS), b"narrow_mask"),
+        (lambda: fill(P, both, ts_base=None), b"ts_base_d"),
+        (lambda: fill(P, both, window_ns=Wfrac), b"window_ns[1]"),
+        (lambda: terminal(_lib.FDX_TERM_COMPACT | _lib.FDX_TERM_RUNS), b"narrow_flag_d"),
+        (lambda: terminal(0), b"narrow_flag_d"),
+        (lambda: terminal(_lib.FDX_TERM_COMPACT, n_windows=2, window_ns=(ctypes.c_int64 * 2)(10**9, 2 * 10**9)),
+         b"n_windows"),
+        (lambda: terminal(_lib.FDX_TERM_COMPACT, delay=1_500_000_000), b"delay_ns"),
+        (lambda: terminal(_lib.FDX_TERM_COMPACT, window_ns=Wfrac), b"window_ns[1]"),
+    ]
+    for i, (call, names) in enumerate(cases):
+        L.fdx_time_flags(None, -1, 0, None, None, None)  # (another message: the one below is this call's)
+        assert call() == -1, (i, L.fdx_last_error())
+        assert names in L.fdx_last_error(), (i, L.fdx_last_error())
 
 
 def _pack(z):

@@ -102,9 +102,9 @@ def test_rekey_sorted_keys_unaligned_output(dev):
 
 @pytest.mark.parametrize("n,n_keys", [(0, 5), (1, 1), (5000, 1), (100_000, 50_000), (300_001, 100_000)])
 def test_rekey_payload_sorted_keys_then_offsets(dev, n, n_keys):
-    """fdx_rekey_payload_keys (the fused step's customer re-key: sorted keys to the caller's
-    buffer, no offsets) + fdx_segment_offsets_sorted == fdx_rekey_payload with offsets: perm,
-    payload, offsets; the id-range count too."""
+    """fdx_rekey_payload with sorted_keys_d (the fused step's customer re-key: sorted keys to the
+    caller's buffer, no offsets) + fdx_segment_offsets_sorted == fdx_rekey_payload with offsets:
+    perm, payload, offsets; the id-range count too."""
     rng = np.random.default_rng(n + 3 * n_keys)
     keys = rng.integers(0, n_keys, size=n).astype(np.int32)
     ts = rng.integers(0, 1 << 60, size=n, dtype=np.int64)
@@ -133,8 +133,8 @@ def test_rekey_payload_sorted_keys_then_offsets(dev, n, n_keys):
                                       (300_001, 100_000), (70_000, 1 << 25)])  # 8- and 9-bit first digits
 def test_rekey_payload_with_first_table_ahead(dev, n, n_keys):
     """fdx_rekey_hist0 (the first pass's scanned table + the id-range count, computed ahead) +
-    fdx_rekey_payload_hist0 == fdx_rekey_payload_checked: perm with the packed flag, payload,
-    offsets and the count of out-of-range ids."""
+    fdx_rekey_payload with hist0_d == fdx_rekey_payload with bad_d: perm with the packed flag,
+    payload, offsets and the count of out-of-range ids."""
     rng = np.random.default_rng(7 * n + n_keys)
     keys = rng.integers(0, n_keys, size=n).astype(np.int32)
     ts = rng.integers(0, 1 << 60, size=n, dtype=np.int64)
@@ -152,6 +152,41 @@ def test_rekey_payload_with_first_table_ahead(dev, n, n_keys):
         if int(b0.item()) == 0:  # (with ids out of range the offsets are unspecified: the caller raises)
             np.testing.assert_array_equal(p1.cpu().numpy() & 0x7FFFFFFF, np.argsort(k, kind="stable"))
             np.testing.assert_array_equal(s1.cpu().numpy(), s0.cpu().numpy())
+
+
+@pytest.mark.parametrize("n_keys", [300, 70_000])  # one 8-bit pass; 17 bits: the 9 + 8 bit plan, two passes
+def test_rekey_payload_no_options_is_a_zeroed_struct(dev, n_keys):
+    """fdx_rekey_payload through ctypes with opts = NULL and with a zeroed fdx_rekey_payload_opts:
+    identical perm, seg_off and both payload columns (three full radix tiles plus a partial one)."""
+    import ctypes
+
+    from fdx import _lib
+
+    L = _lib.load()
+    n = 3 * 4096 + 17
+    kb = ops.key_bits_for(n_keys)
+    rng = np.random.default_rng(n_keys)
+    keys = rng.integers(0, n_keys, size=n).astype(np.int32)
+    kd, ts, amt = T(keys, torch.int32, dev), T(rng.integers(0, 1 << 60, size=n), torch.int64, dev), \
+        T(rng.random(n), torch.float64, dev)
+    ws = ops.workspace(L.fdx_rekey_payload_workspace_size(n, kb, 2), dev)
+    out = []
+    for opts in (None, ctypes.byref(_lib.RekeyPayloadOpts())):
+        perm = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        seg = torch.full((n_keys + 1,), -1, dtype=torch.int64, device=dev)
+        o0, o1 = torch.zeros_like(ts), torch.zeros_like(amt)
+        ops.check(L.fdx_rekey_payload(ops._ptr(kd), n, kb, n_keys, None, ops._ptr(ts), ops._ptr(amt), ops._ptr(perm),
+                                      ops._ptr(seg), ops._ptr(o0), ops._ptr(o1), opts, ops._ptr(ws), ws.numel(), None),
+                  "fdx_rekey_payload")
+        torch.cuda.synchronize()
+        out.append((perm, seg, o0, o1))
+    for a, b in zip(*out):
+        assert torch.equal(a, b)
+    ref = np.argsort(keys, kind="stable")
+    np.testing.assert_array_equal(out[0][0].cpu().numpy(), ref)
+    np.testing.assert_array_equal(out[0][1].cpu().numpy(), np.r_[0, np.cumsum(np.bincount(keys, minlength=n_keys))])
+    np.testing.assert_array_equal(out[0][2].cpu().numpy(), ts.cpu().numpy()[ref])
+    np.testing.assert_array_equal(out[0][3].cpu().numpy().view(np.int64), amt.cpu().numpy()[ref].view(np.int64))
 
 
 def test_argsort_i64_and_perm_ops(dev):
@@ -449,7 +484,7 @@ def test_forest_variants_bit_identical(dev, golden, variant):
 
 
 def test_layout_starts_walk_equals_interleaved(dev):
-    """fdx_customer_layout_starts + fdx_customer_windows_walk (window starts found in the
+    """fdx_customer_layout with window_ns + fdx_customer_windows_walk (window starts found in the
     layout kernel) == fdx_customer_windows_interleaved, bit for bit, incl. a segment longer
     than the 1,024-row LDS stage of the start search."""
     from fdx import synth
@@ -474,9 +509,9 @@ def test_layout_starts_walk_equals_interleaved(dev):
 
 
 def test_layout_plan_fill_equals_layout(dev):
-    """fdx_customer_layout_plan (from fdx_key_segments' offsets, no sort) + _fill_starts_grouped
-    == fdx_customer_layout_starts_grouped: same segment order, slots, rows and window starts
-    (absent customers and a segment longer than the 1,024-row LDS stage included)."""
+    """fdx_customer_layout_plan (from fdx_key_segments' offsets, no sort) + fdx_customer_layout_fill
+    == fdx_customer_layout with FDX_LAYOUT_GROUPED: same segment order, slots, rows and window
+    starts (absent customers and a segment longer than the 1,024-row LDS stage included)."""
     from fdx import synth
 
     d = synth.generate(n_customers=400, n_terminals=500, nb_days=120, seed=32)

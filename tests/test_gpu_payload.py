@@ -7,9 +7,9 @@ streams = the gathered columns, for 1 / 2 / 3 radix passes and tile-edge sizes.
 fdx_terminal_windows_grouped: records / columns against the C oracle, incl. segments longer
 than the 1,024-row LDS stage (a hot terminal, O(L log L) path with the prefix scratch),
 segments of several time-sorted runs (the multi-GPU owner side) and more runs than the per-run
-search handles.  fdx_customer_layout_starts_grouped: identical layout to the gathering form,
-its tiled copy for 1 / 2 / 4 windows (empty customers, a hot one past the start stage) and its
-window starts against numpy's searchsorted."""
+search handles.  fdx_customer_layout with FDX_LAYOUT_GROUPED: identical layout to the gathering
+form, its tiled copy for 1 / 2 / 4 windows (empty customers, a hot one past the start stage) and
+its window starts against numpy's searchsorted."""
 import numpy as np
 import pytest
 import torch
@@ -187,8 +187,8 @@ def test_fused_pipeline_hot_terminal_matches_oracle(dev, golden):
 
 
 def test_compact_records_equal_full_records(dev):
-    """fdx_terminal_windows_grouped_compact: the 16-byte records unpack to the full count
-    records (oracle), for the sorted single-run form and the multi-run owner form."""
+    """fdx_terminal_windows_grouped with FDX_TERM_COMPACT: the 16-byte records unpack to the full
+    count records (oracle), for the sorted single-run form and the multi-run owner form."""
     rng = np.random.default_rng(33)
     ts, term, fraud = _hot_table(rng)
     ref = _oracle_records(ts, fraud, term, 40)

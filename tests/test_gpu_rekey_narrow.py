@@ -1,4 +1,4 @@
-"""The narrow payload re-key (fdx_rekey_payload_narrow): ts as int32 seconds relative to row 0
+"""The narrow payload re-key (fdx_rekey_payload with narrow_flag_d): ts as int32 seconds relative to row 0
 and amount as int32 cents through the radix passes whenever every value has that form exactly,
 decided on the device inside the first pass, with the 8-byte passes as the fallback.
 
@@ -193,7 +193,8 @@ def test_narrow_consumers_refuse_fractional_windows(dev):
     z32 = torch.zeros(n, dtype=torch.int32, device=dev)
     seg = T(np.array([0, n]), torch.int64, dev)
     w = (ops.ctypes.c_int64 * 3)(NS, 1_500_000_000, 2 * NS)
-    rc = L.fdx_terminal_windows_grouped_narrow(ops._ptr(z64), None, ops._ptr(z32), ops._ptr(seg), 1, n, NS, w, 3,
-                                               ops._ptr(z64), ops._ptr(z32), ops._ptr(z32), None)
+    rc = L.fdx_terminal_windows_grouped(ops._ptr(z64), None, ops._ptr(z32), ops._ptr(seg), 1, n, NS, w, 3,
+                                        _lib.FDX_TERM_COMPACT, None, None, ops._ptr(z64), ops._ptr(z32), ops._ptr(z32),
+                                        None)
     assert rc == -1 and b"whole-second" in L.fdx_last_error()  # FDX_E_INVALID
     torch.cuda.synchronize()
