@@ -730,6 +730,40 @@ int fdx_card_precision_top_k(const int32_t *day_d, const int32_t *cust_d, const 
                              int32_t n_days, int32_t top_k, int32_t remove_detected, int32_t *nb_compromised_h,
                              double *cp_h, void *workspace_d, size_t workspace_bytes, void *stream);
 
+/* f-5 score ranking metrics (shared_functions.py:442-460 performance_assessment, called at
+ * model_training.ipynb:2114, :2183, :2252: sklearn's roc_auc_score and average_precision_score;
+ * :523-581 get_class_from_fraud_probability / threshold_based_metrics), on device scores.
+ * fdx_ranking_metrics: label = label_d[i] != 0; rows ordered by score descending; a group is a
+ *   maximal run of scores equal under == (-0.0 and +0.0 are one group, reported as +0.0).
+ *   For group g = 1..m: K_g = rows up to and including it, TP_g = positives among them,
+ *   FP_g = K_g - TP_g; P = TP_m, N = FP_m, index 0 is zero.
+ *     auc_num = sum_g (FP_g - FP_{g-1}) * (TP_g + TP_{g-1})      exact, <= 2PN < 2^61
+ *     auc     = (double)auc_num / (double)(2PN)                  NaN when P = 0 or N = 0
+ *     ap      = (1/P) sum_g (TP_g - TP_{g-1}) * TP_g / K_g       float64; 0.0 when P = 0
+ *   thr_d / tps_d / fps_d (optional, all or none, capacity n each): thresholds (decreasing),
+ *   TP_g and FP_g for g < n_groups: sklearn's _binary_clf_curve.  n_nonfinite counts NaN and
+ *   +-inf scores (sklearn raises on them); when it is nonzero the other fields are unspecified.
+ *   The result is bit-identical between calls and under any permutation of the rows (integer
+ *   sums, and float64 sums in a fixed order; no float atomics).  n in [0, INT32_MAX); no host
+ *   sync, no allocation; workspace: fdx_ranking_metrics_workspace_size(n), 256-byte aligned.
+ * fdx_threshold_counts: counts_d[j] = TN, FP, FN, TP at threshold thr_sorted_d[j], where a row
+ *   is predicted 1 iff not (score < threshold): score == threshold and a NaN score are 1.
+ *   One pass over the rows, no sort.  thr_sorted_d: ascending, no NaN, n_thr <= 1024, else
+ *   FDX_E_INVALID (the thresholds are read back for that check: one host sync of n_thr * 8
+ *   bytes).  workspace: fdx_threshold_counts_workspace_size(n_thr), 8-byte aligned. */
+typedef struct {
+    int64_t n_pos, n_neg, n_groups, n_nonfinite;
+    uint64_t auc_num;
+    double auc, ap;
+} fdx_ranking_result;
+size_t fdx_ranking_metrics_workspace_size(int64_t n);
+int fdx_ranking_metrics(const double *score_d, const uint8_t *label_d, int64_t n, fdx_ranking_result *result_d,
+                        double *thr_d, int64_t *tps_d, int64_t *fps_d, void *workspace_d, size_t workspace_bytes,
+                        void *stream);
+size_t fdx_threshold_counts_workspace_size(int32_t n_thr);
+int fdx_threshold_counts(const double *score_d, const uint8_t *label_d, int64_t n, const double *thr_sorted_d,
+                         int32_t n_thr, int64_t *counts_d, void *workspace_d, size_t workspace_bytes, void *stream);
+
 /* f-3 synthetic transactions with the handbook generator's distributions, on the GPU
  * (fraud_detection_model/data_generator.ipynb :113-140 customers, :285-303 terminals, :420-437
  * terminals within radius, :786-834 daily Poisson transactions, :1339-1371 time sort, :1732-1782

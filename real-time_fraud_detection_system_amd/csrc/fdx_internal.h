@@ -97,4 +97,13 @@ inline unsigned stream_grid(int64_t n, int block, int64_t cap = 256 * 8) {
     return (unsigned)g;
 }
 
+// The stable 64-bit LSD radix sort of fdx_rekey.hip (the one behind fdx_argsort_i64), for the
+// other translation units: ascending over all 64 bits of keys_d, n in [1, INT32_MAX).
+// *sorted_d = the sorted keys and *vals_d = per sorted position the input row index with
+// bit 31 = flag_d[row] != 0; both lie inside workspace_d (sort_u64_flag_workspace_size(n) bytes,
+// 256-byte aligned).
+size_t sort_u64_flag_workspace_size(int64_t n);
+int sort_u64_flag(const uint64_t *keys_d, const uint8_t *flag_d, int64_t n, void *workspace_d, hipStream_t st,
+                  const uint64_t **sorted_d, const uint32_t **vals_d);
+
 }  // namespace fdx

@@ -813,6 +813,21 @@ int radix_sort(const K *keys, int64_t n, int bits, K flip, K *keys_out, uint32_t
 }
 
 }  // namespace
+
+// fdx_internal.h: the 64-bit sort for the other translation units (fdx_metrics.hip)
+size_t sort_u64_flag_workspace_size(int64_t n) {
+    return sort_ws<uint64_t>(n, nullptr, nullptr) + align_up(sizeof(uint32_t) * (size_t)n);
+}
+
+int sort_u64_flag(const uint64_t *keys_d, const uint8_t *flag_d, int64_t n, void *workspace_d, hipStream_t st,
+                  const uint64_t **sorted_d, const uint32_t **vals_d) {
+    SortWs<uint64_t> w;
+    char *ws = reinterpret_cast<char *>(workspace_d);
+    uint32_t *vals = reinterpret_cast<uint32_t *>(ws + sort_ws<uint64_t>(n, &w, ws));
+    *vals_d = vals;
+    return radix_sort<uint64_t>(keys_d, n, 64, 0ull, nullptr, vals, w, st, sorted_d, 0, flag_d);
+}
+
 }  // namespace fdx
 
 using namespace fdx;

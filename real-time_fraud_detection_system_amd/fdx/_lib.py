@@ -64,6 +64,12 @@ class RekeyPayloadOpts(ctypes.Structure):
                 ("narrow_mask", c_i32)]
 
 
+class RankingResult(ctypes.Structure):
+    """fdx_ranking_result (include/fdx.h)"""
+    _fields_ = [("n_pos", c_i64), ("n_neg", c_i64), ("n_groups", c_i64), ("n_nonfinite", c_i64),
+                ("auc_num", ctypes.c_uint64), ("auc", ctypes.c_double), ("ap", ctypes.c_double)]
+
+
 # name -> (restype, argtypes); exactly the symbols declared in include/fdx.h
 SIGNATURES = {
     "fdx_last_error": (ctypes.c_char_p, []),
@@ -105,6 +111,10 @@ SIGNATURES = {
     "fdx_card_precision_workspace_size": (ctypes.c_size_t, [c_i32]),
     "fdx_card_precision_top_k": (ctypes.c_int, [P, P, P, P, c_i64, c_i32, P, c_i32, c_i32, c_i32, P, P, P, c_sz,
                                                 P]),
+    "fdx_ranking_metrics_workspace_size": (c_sz, [c_i64]),
+    "fdx_ranking_metrics": (ctypes.c_int, [P, P, c_i64, P, P, P, P, P, c_sz, P]),
+    "fdx_threshold_counts_workspace_size": (c_sz, [c_i32]),
+    "fdx_threshold_counts": (ctypes.c_int, [P, P, c_i64, P, c_i32, P, P, c_sz, P]),
     "fdx_invert_perm": (ctypes.c_int, [P, c_i64, P, P]),
     "fdx_rekey_workspace_size": (c_sz, [c_i64, c_i32]),
     "fdx_rekey": (ctypes.c_int, [P, c_i64, c_i32, c_i64, P, P, P, P, c_sz, P]),

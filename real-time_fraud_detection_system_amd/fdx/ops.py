@@ -952,3 +952,63 @@ def forest_arrays_from_sklearn(model) -> dict:
     return dict(left=np.concatenate(left), right=np.concatenate(right), feature=np.concatenate(feat),
                 threshold=np.concatenate(thr), missing_left=np.concatenate(ml), value1=np.concatenate(val),
                 value0=np.concatenate(val0), node_offsets=np.asarray(off, np.int64))
+
+
+class RankingMetrics:
+    """Device result of ranking_metrics: `result` holds one fdx_ranking_result (56 bytes); with
+    curve=True, `thresholds` / `tps` / `fps` hold the curve points g < n_groups (capacity n).
+    Nothing is read back until host() or curve()."""
+
+    def __init__(self, result, thresholds=None, tps=None, fps=None):
+        self.result, self.thresholds, self.tps, self.fps = result, thresholds, tps, fps
+
+    def host(self) -> dict:
+        """The result's fields as Python numbers (one device-to-host copy of 56 bytes)."""
+        r = _lib.RankingResult.from_buffer_copy(self.result.cpu().numpy().tobytes())
+        return {name: getattr(r, name) for name, _ in _lib.RankingResult._fields_}
+
+    def curve(self):
+        """(fps, tps, thresholds) device tensors of length n_groups (reads n_groups back)."""
+        if self.thresholds is None:
+            raise FdxError("ranking_metrics was called without curve=True")
+        m = self.host()["n_groups"]
+        return self.fps[:m], self.tps[:m], self.thresholds[:m]
+
+
+def ranking_metrics(scores: torch.Tensor, labels: torch.Tensor, curve: bool = False, stream=None) -> RankingMetrics:
+    """AUC ROC and average precision of device scores (float64) against labels (uint8, != 0 is
+    positive): fdx_ranking_metrics.  FraudPipeline.run_fused's output and the fraud column go
+    straight in; no host copy, no sync."""
+    _dev(scores, torch.float64, "scores")
+    _dev(labels, torch.uint8, "labels")
+    n = scores.numel()
+    if labels.numel() != n:
+        raise FdxError(f"labels has {labels.numel()} rows, scores {n}")
+    dev = scores.device
+    res = torch.empty(ctypes.sizeof(_lib.RankingResult), dtype=torch.uint8, device=dev)
+    thr = torch.empty(n, dtype=torch.float64, device=dev) if curve else None
+    tps = torch.empty(n, dtype=torch.int64, device=dev) if curve else None
+    fps = torch.empty(n, dtype=torch.int64, device=dev) if curve else None
+    L = _lib.load()
+    ws = workspace(L.fdx_ranking_metrics_workspace_size(n), dev)
+    check(L.fdx_ranking_metrics(_ptr(scores), _ptr(labels), n, _ptr(res), _ptr(thr), _ptr(tps), _ptr(fps), _ptr(ws),
+                                ws.numel(), _s(stream)), "fdx_ranking_metrics")
+    return RankingMetrics(res, thr, tps, fps)
+
+
+def threshold_counts(scores: torch.Tensor, labels: torch.Tensor, thresholds: torch.Tensor, stream=None) -> torch.Tensor:
+    """int64 [n_thr, 4] device tensor of TN, FP, FN, TP per threshold, a row predicted 1 iff not
+    (score < threshold): fdx_threshold_counts.  thresholds: float64 on the device, ascending, no
+    NaN, at most 1,024 (the library reads them back to check: one small host sync)."""
+    _dev(scores, torch.float64, "scores")
+    _dev(labels, torch.uint8, "labels")
+    _dev(thresholds, torch.float64, "thresholds")
+    n, n_thr = scores.numel(), thresholds.numel()
+    if labels.numel() != n:
+        raise FdxError(f"labels has {labels.numel()} rows, scores {n}")
+    counts = torch.empty((n_thr, 4), dtype=torch.int64, device=scores.device)
+    L = _lib.load()
+    ws = workspace(L.fdx_threshold_counts_workspace_size(min(n_thr, 1024)), scores.device)
+    check(L.fdx_threshold_counts(_ptr(scores), _ptr(labels), n, _ptr(thresholds), n_thr, _ptr(counts), _ptr(ws),
+                                 ws.numel(), _s(stream)), "fdx_threshold_counts")
+    return counts
