@@ -162,6 +162,19 @@ int fdx_customer_windows_scan_slots(const double *gamount_d, const int64_t *seg_
 int fdx_customer_windows_walk(const double *iamt_d, const int64_t *seg_off_d, const int32_t *sorder_d,
                               const uint32_t *goff_d, int64_t n_seg, int64_t n_slots, int32_t n_windows,
                               const int32_t *starts_d, int32_t *nb_d, double *sum_d, void *stream);
+/* The same walk writing into planes the caller places: window w's counts at nb_d + w * nb_stride,
+ * its values at val_d + w * val_stride (strides in ELEMENTS, each >= n_slots; the walk above is
+ * nb_stride = val_stride = n_slots).  With the strides of a slot-order feature table -- nb_d / val_d
+ * its FDX_FEATURE_COL(0) / FDX_FEATURE_COL(6) columns, both strides its cap -- the customer columns
+ * land in the table once (fdx_forest_prepare_grouped, FDX_PREP_CUST_IN_TABLE).  val_is_avg: the value
+ * stored is the average, sum / (double)nb -- the IEEE float64 division the row assembly does under
+ * FDX_PREP_VAL_IS_SUM, bit for bit (nb = 0: NaN / 0.0) -- done per chunk beside the stores, after the
+ * recurrence; 0: the rolling sum.  Only slots of the layout's segments are written: padding slots and
+ * everything between n_slots and the stride keep their bytes. */
+int fdx_customer_windows_walk_strided(const double *iamt_d, const int64_t *seg_off_d, const int32_t *sorder_d,
+                                      const uint32_t *goff_d, int64_t n_seg, int64_t n_slots, int32_t n_windows,
+                                      const int32_t *starts_d, int32_t *nb_d, int64_t nb_stride, double *val_d,
+                                      int64_t val_stride, int32_t val_is_avg, void *stream);
 /* fdx_customer_windows over that layout: nb_d / sum_d are [W][n_slots] indexed by slot, with
  * sum_d the rolling SUM (pandas roll_sum, bit-exact); the average is sum / nb (IEEE float64
  * division, done by the consumer -- fdx_forest_prepare_grouped with FDX_PREP_VAL_IS_SUM --
@@ -564,6 +577,18 @@ int fdx_forest_prepare_reply(fdx_forest forest, const int64_t *reply_d, const in
                                    (earlier, e.g. on another stream): no clearing memset here   */
 #define FDX_PREP_INDEX64 16     /* the row kernel's 64-bit slot arithmetic even where n fits 32 bits
                                    (what n near 2^31 takes; same results -- for tests and A/B)   */
+#define FDX_PREP_CUST_IN_TABLE 32 /* the customer columns already sit in the slot-order table out_d: cust_nb_d,
+                                   cust_avg_d (AVERAGES) and cust_perm_d are NOT read -- the call takes them
+                                   from columns 0-2, 6-8 and 12 of out_d at stride out_cap (written there by
+                                   fdx_customer_windows_walk_strided(val_is_avg = 1) and by
+                                   fdx_customer_layout_fill with irow_d = column 12) and does not store them
+                                   again: a live slot gets term_nb, term_risk and the flags only (38 B).
+                                   Padding slots -- cust_perm < 0 inside [0, n) and the tail [n,
+                                   round_up(n, 64)), which the walk never touches -- get row -1 and zeros in
+                                   the six customer columns here, so the table's contract holds in a reused
+                                   buffer.  Needs rows_order = FDX_ROWS_SLOT_ORDER, n_windows = 3, the rank
+                                   layout's row kernel (k_zfill_grouped_w3) and a table below 2^31 bytes; not
+                                   with FDX_PREP_VAL_IS_SUM.  Anything else: FDX_E_INVALID, nothing enqueued */
 /* Clears the NaN flag of a forest workspace sized for n rows (a 4-byte memset on `stream`): with
  * FDX_PREP_FLAG_CLEARED, the prepare call that follows skips its own clearing -- the scoring step
  * enqueues this off its critical path (fdx.pipeline). */
@@ -605,6 +630,10 @@ int fdx_forest_prepare_grouped(fdx_forest forest, int64_t n, int32_t n_windows, 
                                const double *cust_avg_d, const int32_t *cust_perm_d, const int32_t *term_inv_d,
                                const int64_t *term_rec_d, void *out_d, int64_t out_cap, int32_t rows_order,
                                void *workspace_d, size_t workspace_bytes, void *stream);
+/* 1 when fdx_forest_prepare_grouped accepts FDX_PREP_CUST_IN_TABLE for this forest (in its current
+ * variant), n_windows and a slot-order table of out_cap slots per column; 0 otherwise (a caller then
+ * keeps the customer columns in buffers of its own).  No GPU work. */
+int fdx_forest_prepare_in_table_ok(fdx_forest forest, int32_t n_windows, int64_t out_cap);
 /* fdx_forest_traverse writing proba_d[out_perm_d[row]] (and leaf rows likewise). */
 int fdx_forest_traverse_perm(fdx_forest forest, int64_t n, double *proba_d, const int32_t *out_perm_d,
                              int32_t *leaf_d, void *workspace_d, size_t workspace_bytes, void *stream);

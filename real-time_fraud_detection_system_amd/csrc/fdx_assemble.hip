@@ -628,6 +628,8 @@ __global__ void __launch_bounds__(kPrepStBlock) k_prepare_st(const double *__res
     }
 }
 
+typedef unsigned int fdx_u32x2_t __attribute__((ext_vector_type(2)));
+
 struct PrepRow {
     int64_t t;
     double a;
@@ -677,14 +679,31 @@ __device__ __forceinline__ void decode_tw(const int64_t *rec, PrepRow &L) {
 // it at the top of every row: the reload's s_waitcnt vmcnt(0) waited there for the previous row's
 // stores and for the prefetched loads -- the wait the notes above are about (1.195 -> 1.147 ms in
 // step at config 2, profiles/r07_assembly_scalar_ab.txt).  false: the 64-bit form, for n beyond.
+// EMIT = kEmitSlotInTable (FDX_PREP_CUST_IN_TABLE): the slot-order table already holds the customer
+// columns -- the walk stored cust_nb / cust_avg (averages), the layout fill the row -- so cnb / cval /
+// cust_perm are those columns of `feat` (stride fcap), a live slot stores term_nb, term_risk and the
+// flags only, and the non-live slots (padding inside [0, n), the tail up to round_up(n, 64)), which
+// the walk never writes and a reused buffer leaves stale, get their zeros and row -1 by raw buffer
+// stores whose offset is out of range for live lanes (k_customer_walk's pattern: no branch around
+// stores, see above).  The host keeps the table below 2^31 bytes (32-bit buffer offsets).
+constexpr int kEmitSlotInTable = 3;
+static_assert(kEmitSlotInTable != FDX_ROWS_INPUT_ORDER && kEmitSlotInTable != FDX_ROWS_SLOT_ORDER, "own value");
 template <int EMIT, bool COMPACT, bool TINV, bool I32>
 __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
-    const int64_t *__restrict__ cts, const double *__restrict__ camt, const int32_t *__restrict__ cnb,
-    const double *__restrict__ cval, const int32_t *__restrict__ cust_perm, const int32_t *__restrict__ term_inv,
+    const int64_t *__restrict__ cts, const double *__restrict__ camt, const int32_t *__restrict__ cnb_,
+    const double *__restrict__ cval_, const int32_t *__restrict__ cust_perm_, const int32_t *__restrict__ term_inv,
     const int64_t *__restrict__ term_rec, int64_t n, int32_t flags_mode, int32_t val_is_sum,
     const double *__restrict__ mean, const double *__restrict__ scale, void *__restrict__ z,
     int32_t *__restrict__ nan_flag, RankTab rt, char *__restrict__ feat, int64_t fcap) {
     constexpr int W = 3, nf = 15;
+    constexpr bool INTBL = EMIT == kEmitSlotInTable;
+    constexpr bool SLOTS = EMIT == FDX_ROWS_SLOT_ORDER || INTBL;
+    // (in the table: derived from `feat`, the pointer the padding stores go through)
+    const int32_t *cnb = INTBL ? reinterpret_cast<const int32_t *>(feat + FDX_FEATURE_COL(0, fcap)) : cnb_;
+    const double *cval = INTBL ? reinterpret_cast<const double *>(feat + FDX_FEATURE_COL(6, fcap)) : cval_;
+    const int32_t *cust_perm = INTBL ? reinterpret_cast<const int32_t *>(feat + FDX_FEATURE_COL(12, fcap)) : cust_perm_;
+    const int64_t cstride = INTBL ? fcap : n;  // elements between the window planes of cnb / cval
+    const bool is_sum = !INTBL && (val_is_sum & 1);  // (in the table: averages, no division compiled in)
     static_assert(sizeof(fdx_feature_row) == 80, "5 x 16-byte stores per feature record");
     __shared__ __align__(16) float s_t[kW3TreeFloats];  // the S-trees (RankTab::etab)
     __shared__ uint16_t s_itab[16 * kIntTab];
@@ -717,8 +736,8 @@ __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
         L.a = camt[jj];
 #pragma unroll
         for (int w = 0; w < W; ++w) {
-            L.c[w] = cnb[(int64_t)w * n + jj];
-            L.cv[w] = cval[(int64_t)w * n + jj];
+            L.c[w] = cnb[(int64_t)w * cstride + jj];
+            L.cv[w] = cval[(int64_t)w * cstride + jj];
         }
         if constexpr (COMPACT) {
             L.raw = *reinterpret_cast<const longlong2 *>(term_rec + 2 * qq);
@@ -806,19 +825,41 @@ __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
             // +0.62 ms at config 2; padding slots: row -1, zero features)
             // (slot order: every lane stores, i < round_up(n, 64) <= fcap -- no branch, so that
             // no wait behind it has to assume the stores were skipped)
-            if (EMIT == FDX_ROWS_SLOT_ORDER || (i < n && live && (uint64_t)cur.r < (uint64_t)fcap)) {
+            if (SLOTS || (i < n && live && (uint64_t)cur.r < (uint64_t)fcap)) {
                 auto u32 = [](double d, int h) { return (uint32_t)((uint64_t)__double_as_longlong(d) >> (32 * h)); };
                 uint32_t c[W], tn[W];
                 double avg[W], rk[W];
 #pragma unroll
                 for (int w = 0; w < W; ++w) {
                     c[w] = live ? (uint32_t)cur.c[w] : 0u;
-                    avg[w] = !live ? 0.0 : (val_is_sum & 1) ? cur.cv[w] / (double)cur.c[w] : cur.cv[w];
+                    avg[w] = !live ? 0.0 : is_sum ? cur.cv[w] / (double)cur.c[w] : cur.cv[w];
                     tn[w] = live ? (uint32_t)term_nb(cur.tw[w]) : 0u;
                     rk[w] = live ? term_risk(cur.tw[w]) : 0.0;
                 }
                 const uint32_t fl = live ? ((uint32_t)we | (uint32_t)ni << 8) : 0u;
-                if constexpr (EMIT == FDX_ROWS_SLOT_ORDER) {
+                if constexpr (INTBL) {
+#pragma unroll
+                    for (int w = 0; w < W; ++w) {
+                        fst(reinterpret_cast<uint32_t *>(feat + FDX_FEATURE_COL(3 + w, fcap)) + i, tn[w]);
+                        fst(reinterpret_cast<double *>(feat + FDX_FEATURE_COL(9 + w, fcap)) + i, rk[w]);
+                    }
+                    fst(reinterpret_cast<uint16_t *>(feat + FDX_FEATURE_COL(13, fcap)) + i, (uint16_t)fl);
+                    // the customer columns of a NON-live slot (i < round_up(n, 64) <= fcap): zeros and
+                    // row -1; a live lane's offset is out of range and its stores are dropped
+                    const __amdgpu_buffer_rsrc_t rft = __builtin_amdgcn_make_buffer_rsrc(
+                        feat, (short)0, (int)(FDX_FEATURE_COL(12, fcap) + 4 * fcap), 0x00020000);
+                    const uint32_t i4 = (uint32_t)i * 4u, dead = 0x80000000u;
+#pragma unroll
+                    for (int w = 0; w < W; ++w) {
+                        __builtin_amdgcn_raw_buffer_store_b32(
+                            0u, rft, (int)(live ? dead : (uint32_t)FDX_FEATURE_COL(w, fcap) + i4), 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(
+                            fdx_u32x2_t{0u, 0u}, rft, (int)(live ? dead : (uint32_t)FDX_FEATURE_COL(6 + w, fcap) + 2u * i4),
+                            0, 0);
+                    }
+                    __builtin_amdgcn_raw_buffer_store_b32(
+                        0xFFFFFFFFu, rft, (int)(live ? dead : (uint32_t)FDX_FEATURE_COL(12, fcap) + i4), 0, 0);
+                } else if constexpr (EMIT == FDX_ROWS_SLOT_ORDER) {
 #pragma unroll
                     for (int w = 0; w < W; ++w) {
                         fst(reinterpret_cast<uint32_t *>(feat + FDX_FEATURE_COL(w, fcap)) + i, c[w]);
@@ -844,7 +885,7 @@ __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
         for (int w = 0; w < W; ++w) {
             const int32_t c = cur.c[w];
             count(3 + 2 * w, c);
-            v[4 + 2 * w] = zs((val_is_sum & 1) ? cur.cv[w] / (double)c : cur.cv[w], 4 + 2 * w);
+            v[4 + 2 * w] = zs(is_sum ? cur.cv[w] / (double)c : cur.cv[w], 4 + 2 * w);
             nan |= v[4 + 2 * w] != v[4 + 2 * w];
             const int64_t tw = cur.tw[w];
             const int32_t tnb = term_nb(tw), tfr = (int32_t)((uint64_t)tw >> 32);
@@ -1180,6 +1221,16 @@ extern "C" int fdx_forest_clear_flag(fdx_forest F, int64_t n, void *ws, size_t w
     return FDX_OK;
 }
 
+// k_zfill_grouped_w3 serves this forest and window count (else: k_zfill_grouped + k_feature_rows)
+static bool w3_rows(const fdx_forest_s *F, int32_t n_windows) {
+    return rank_mode(F) && n_windows == 3 && F->rrat_d && F->rnetab > 0 && F->retab_d;
+}
+
+extern "C" int fdx_forest_prepare_in_table_ok(fdx_forest F, int32_t n_windows, int64_t out_cap) {
+    return F && w3_rows(F, n_windows) && !v2_rows(kVariants[F->variant].p16) && F->n_features == 15 && out_cap > 0 &&
+           out_cap % 64 == 0 && FDX_FEATURE_TABLE_BYTES(out_cap) < (int64_t)INT32_MAX;
+}
+
 extern "C" int fdx_forest_prepare_grouped(fdx_forest F, int64_t n, int32_t n_windows, int32_t flags_mode, int32_t opts,
                                           const int64_t *cust_ts_d, const double *cust_amount_d,
                                           const int32_t *cust_nb_d, const double *cust_avg_d,
@@ -1199,10 +1250,21 @@ extern "C" int fdx_forest_prepare_grouped(fdx_forest F, int64_t n, int32_t n_win
     FDX_REQUIRE(flags_mode == FDX_FLAGS_NOTEBOOK || flags_mode == FDX_FLAGS_SPARK, "bad flags mode");
     FDX_REQUIRE(F->n_features == 3 + 4 * n_windows, "forest has %d features, expected %d", F->n_features,
                 3 + 4 * n_windows);
+    const bool in_table = (opts & FDX_PREP_CUST_IN_TABLE) != 0;
+    const RankTab rt = rank_tab(F);
+    const bool w3 = w3_rows(F, n_windows);
+    if (in_table) {
+        FDX_REQUIRE(rows_out_d && rows_order == FDX_ROWS_SLOT_ORDER,
+                    "FDX_PREP_CUST_IN_TABLE: the customer columns are read from a slot-order table (out_d)");
+        FDX_REQUIRE(!(opts & FDX_PREP_VAL_IS_SUM), "FDX_PREP_CUST_IN_TABLE: the table holds averages, not sums");
+        FDX_REQUIRE(w3, "FDX_PREP_CUST_IN_TABLE: 3 windows and the rank layout's row kernel only");
+        FDX_REQUIRE(FDX_FEATURE_TABLE_BYTES(out_cap) < (int64_t)INT32_MAX,
+                    "FDX_PREP_CUST_IN_TABLE: a table of %lld slots per column exceeds 2^31 bytes", (long long)out_cap);
+    }
     if (n == 0) return FDX_OK;
-    FDX_REQUIRE(cust_ts_d && cust_amount_d && cust_nb_d && cust_avg_d && term_rec_d, "null pointer");
-    FDX_REQUIRE((opts & ~29) == 0,
-                "opts: FDX_PREP_VAL_IS_SUM | FDX_PREP_TERM_COMPACT | FDX_PREP_FLAG_CLEARED | FDX_PREP_INDEX64 only");
+    FDX_REQUIRE(cust_ts_d && cust_amount_d && term_rec_d && (in_table || (cust_nb_d && cust_avg_d)), "null pointer");
+    FDX_REQUIRE((opts & ~61) == 0, "opts: FDX_PREP_VAL_IS_SUM | FDX_PREP_TERM_COMPACT | FDX_PREP_FLAG_CLEARED | "
+                                   "FDX_PREP_INDEX64 | FDX_PREP_CUST_IN_TABLE only");
     FDX_REQUIRE(!(opts & 4) || (n_windows == 3 && ((uintptr_t)term_rec_d & 15) == 0),
                 "compact terminal records: W = 3 and a 16-byte aligned record array");
     float *z;
@@ -1214,10 +1276,9 @@ extern "C" int fdx_forest_prepare_grouped(fdx_forest F, int64_t n, int32_t n_win
     if (!(opts & FDX_PREP_FLAG_CLEARED)) FDX_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
     opts &= ~FDX_PREP_FLAG_CLEARED;
     const bool index64 = (opts & FDX_PREP_INDEX64) != 0;
-    opts &= ~FDX_PREP_INDEX64;
+    opts &= ~(FDX_PREP_INDEX64 | FDX_PREP_CUST_IN_TABLE);
     const unsigned grid = stream_grid(n, 256);
-    const RankTab rt = rank_tab(F);
-    if (rank_mode(F) && n_windows == 3 && rt.rat && rt.etab) {
+    if (w3) {
 #define FDX_ZFILL_W3_I(E, C, T, I)                                                                                \
     hipLaunchKernelGGL((k_zfill_grouped_w3<E, C, T, I>), dim3(grid_w3), dim3(kW3Block), 0, st, cust_ts_d,          \
                        cust_amount_d, cust_nb_d, cust_avg_d, cust_perm_d, term_inv_d, term_rec_d, n, flags_mode,    \
@@ -1240,6 +1301,8 @@ extern "C" int fdx_forest_prepare_grouped(fdx_forest F, int64_t n, int32_t n_win
         const bool i32 = !index64 && n + 4 * (int64_t)grid_w3 * kW3Block <= (int64_t)INT32_MAX;
         if (!rows_out_d)
             FDX_ZFILL_W3_E(0);
+        else if (in_table)
+            FDX_ZFILL_W3_E(kEmitSlotInTable);
         else if (rows_order == FDX_ROWS_SLOT_ORDER)
             FDX_ZFILL_W3_E(FDX_ROWS_SLOT_ORDER);
         else

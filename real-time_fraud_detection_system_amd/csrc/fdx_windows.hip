@@ -813,13 +813,38 @@ __global__ void __launch_bounds__(64) k_customer_ring(
 // out-of-range offset (the store is dropped) instead of a branch: behind a branch around stores,
 // the next chunk's wait for its prefetched amounts had to assume the stores were skipped and
 // waited for them too (vmcnt counts stores).  Needs the outputs within 2^31 bytes (the host picks).
+// Strided (none, or one WalkStrided<AVG> argument behind lg_max): where the per-row outputs go.
+// None: nb_out / sum_out are [n_win][n_slots] planes of their own (fdx_customer_windows_walk; the
+// kernel is then what it was before the argument existed).  WalkStrided: window w's plane starts
+// nb_stride / val_stride elements after window w - 1's (the columns of a slot-order feature table,
+// fdx_customer_windows_walk_strided), the value stored being the rolling sum or, with AVG, the
+// average sum / nb: the row assembly's IEEE division, done in the chunk's output stage beside the
+// stores -- after the chunk's recurrence, never inside it.
 typedef unsigned int fdx_u32x2 __attribute__((ext_vector_type(2)));
-template <int S_MAX, int kRing, int P, bool BUF, int kChunk = fdx::kChunk>
+template <bool AVG>
+struct WalkStrided {
+    int64_t nb_stride, val_stride;
+};
+template <typename... T>
+struct WalkOut {  // the planes of the walk's own
+    static constexpr bool kStrided = false, kAvg = false;
+    __device__ static int64_t nb_stride(int64_t n_slots) { return n_slots; }
+    __device__ static int64_t val_stride(int64_t n_slots) { return n_slots; }
+};
+template <bool AVG>
+struct WalkOut<WalkStrided<AVG>> {
+    static constexpr bool kStrided = true, kAvg = AVG;
+    __device__ static int64_t nb_stride(int64_t, WalkStrided<AVG> s) { return s.nb_stride; }
+    __device__ static int64_t val_stride(int64_t, WalkStrided<AVG> s) { return s.val_stride; }
+};
+template <int S_MAX, int kRing, int P, bool BUF, int kChunk = fdx::kChunk, typename... Strided>
 __global__ void __launch_bounds__(64) k_customer_walk(
     const double *__restrict__ iamt, const int64_t *__restrict__ seg_off, const int32_t *__restrict__ sorder,
     const uint32_t *__restrict__ goff, int64_t n_seg, int32_t S, int64_t n_slots, int32_t n_win,
     int32_t *__restrict__ nb_out, double *__restrict__ sum_out, const int32_t *__restrict__ starts,
-    int32_t lg_min = 0, int32_t lg_max = INT32_MAX) {
+    int32_t lg_min, int32_t lg_max, Strided... strided) {
+    using Out = WalkOut<Strided...>;
+    const int64_t nbs = Out::nb_stride(n_slots, strided...), vls = Out::val_stride(n_slots, strided...);
     static_assert((kRing & (kRing - 1)) == 0 && kRing % kChunk == 0, "power-of-two ring of whole chunks");
     constexpr int kPer = (kChunk * S_MAX + kWave - 1) / kWave;  // chunk elements per lane
     constexpr int kRingEl = kRing * S_MAX + kWave;             // + one miss slot per lane
@@ -843,11 +868,14 @@ __global__ void __launch_bounds__(64) k_customer_walk(
     const int32_t L = active ? (int32_t)(seg_off[s + 1] - seg_off[s]) : 0;
     const int64_t gbase = goff[g];
     const double *g_amt = iamt + gbase + seg0 + l;  // row t of this lane's segment: g_amt[t * S]
-    int32_t *nb = nb_out + (int64_t)wi * n_slots + gbase + seg0 + l;
-    double *sm = sum_out + (int64_t)wi * n_slots + gbase + seg0 + l;
-    const int32_t n_out = (int32_t)imin64((int64_t)n_win * n_slots, INT32_MAX / 8);
+    int32_t *nb = nb_out + (int64_t)wi * nbs + gbase + seg0 + l;
+    double *sm = sum_out + (int64_t)wi * vls + gbase + seg0 + l;
+    // (strided: the last window's plane ends n_slots past its start, whatever lies behind it)
+    const int32_t n_out = (int32_t)imin64(Out::kStrided ? (int64_t)(n_win - 1) * nbs + n_slots : (int64_t)n_win * n_slots,
+                                          INT32_MAX / 8);
+    const int32_t n_outv = Out::kStrided ? (int32_t)imin64((int64_t)(n_win - 1) * vls + n_slots, INT32_MAX / 8) : n_out;
     const __amdgpu_buffer_rsrc_t rnb = __builtin_amdgcn_make_buffer_rsrc(nb_out, (short)0, n_out * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsm = __builtin_amdgcn_make_buffer_rsrc(sum_out, (short)0, n_out * 8, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsm = __builtin_amdgcn_make_buffer_rsrc(sum_out, (short)0, n_outv * 8, 0x00020000);
     // chunk element e = lane + j * 64 of this wave's Sw segments: row e / Sw, segment e % Sw --
     // the same for every chunk, so its slot offset and ring position are computed once
     int32_t e_src[kPer], e_ring[kPer];
@@ -995,15 +1023,21 @@ __global__ void __launch_bounds__(64) k_customer_walk(
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if constexpr (Out::kAvg) {  // (a lane past its segment's end divides stale values: never stored)
+#pragma unroll
+            for (int j = 0; j < kChunk; ++j) oval[j] = oval[j] / (double)onb[j];
+        }
         if constexpr (BUF) {
-            const uint32_t o0 = (uint32_t)((int64_t)wi * n_slots + gbase + seg0 + l);  // element index of row 0
+            const uint32_t o0 = (uint32_t)((int64_t)wi * nbs + gbase + seg0 + l);  // element index of row 0
+            const uint32_t o0v = Out::kStrided ? (uint32_t)((int64_t)wi * vls + gbase + seg0 + l) : o0;
 #pragma unroll
             for (int j = 0; j < kChunk; ++j) {
                 const bool ok = t0 + j < L;
                 const uint32_t el = o0 + (uint32_t)(t0 + j) * (uint32_t)S;
+                const uint32_t elv = Out::kStrided ? o0v + (uint32_t)(t0 + j) * (uint32_t)S : el;
                 __builtin_amdgcn_raw_buffer_store_b32(onb[j], rnb, ok ? (int)(el * 4u) : (int)0x80000000, 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(fdx_u32x2, oval[j]), rsm,
-                                                      ok ? (int)(el * 8u) : (int)0x80000000, 0, 0);
+                                                      ok ? (int)(elv * 8u) : (int)0x80000000, 0, 0);
             }
         } else {
 #pragma unroll
@@ -2234,6 +2268,53 @@ extern "C" int fdx_customer_windows_walk(const double *iamt_d, const int64_t *se
     FDX_HIP(hipStreamWaitEvent(st, f->join, 0));
     return FDX_OK;
 #undef FDX_WALK
+}
+
+extern "C" int fdx_customer_windows_walk_strided(const double *iamt_d, const int64_t *seg_off_d,
+                                                 const int32_t *sorder_d, const uint32_t *goff_d, int64_t n_seg,
+                                                 int64_t n_slots, int32_t n_windows, const int32_t *starts_d,
+                                                 int32_t *nb_d, int64_t nb_stride, double *val_d, int64_t val_stride,
+                                                 int32_t val_is_avg, void *stream) {
+    FDX_REQUIRE(n_seg >= 0 && n_slots >= 0, "negative size");
+    FDX_REQUIRE(n_windows >= 1 && n_windows <= FDX_MAX_WINDOWS, "bad n_windows");
+    FDX_REQUIRE(nb_stride >= n_slots && val_stride >= n_slots, "plane strides %lld / %lld below n_slots = %lld",
+                (long long)nb_stride, (long long)val_stride, (long long)n_slots);
+    if (n_seg == 0) return FDX_OK;
+    FDX_REQUIRE(iamt_d && seg_off_d && sorder_d && goff_d && starts_d && nb_d && val_d, "null pointer");
+    const int32_t S = kWave / n_windows;
+    FDX_REQUIRE(S <= 21, "the walk kernel is built for <= 21 segments per wave (>= 3 windows)");
+    const int64_t n_groups = ceil_div(n_seg, S);
+    hipStream_t st = as_stream(stream);
+    constexpr int split = kWalkSplitRows;  // the length classes of fdx_customer_windows_walk
+    // buffer stores while the strided outputs fit 2^31 bytes (raw buffer offsets are 32-bit)
+    const int64_t smax = nb_stride > val_stride ? nb_stride : val_stride;
+    const bool buf = (int64_t)n_windows * smax * 8 < (int64_t)INT32_MAX / 8 * 8;
+    const bool avg = val_is_avg != 0;
+#define FDX_WALK_K(SM, RING, P, B, A, STREAM, LO, HI)                                                          \
+    hipLaunchKernelGGL((k_customer_walk<SM, RING, P, B, kWalkChunk, WalkStrided<A>>), dim3((unsigned)(n_groups * (P))), \
+                       dim3(64), 0, STREAM, iamt_d, seg_off_d, sorder_d, goff_d, n_seg, S, n_slots, n_windows, nb_d, \
+                       val_d, starts_d, LO, HI, WalkStrided<A>{nb_stride, val_stride})
+#define FDX_WALK(SM, RING, P, STREAM, LO, HI)                                                                  \
+    if (buf) {                                                                                                 \
+        if (avg) FDX_WALK_K(SM, RING, P, true, true, STREAM, LO, HI);                                          \
+        else FDX_WALK_K(SM, RING, P, true, false, STREAM, LO, HI);                                             \
+    } else {                                                                                                   \
+        if (avg) FDX_WALK_K(SM, RING, P, false, true, STREAM, LO, HI);                                         \
+        else FDX_WALK_K(SM, RING, P, false, false, STREAM, LO, HI);                                            \
+    }                                                                                                          \
+    FDX_LAUNCHED("k_customer_walk<WalkStrided>")
+    ForkStream *f;
+    int rc = fork_stream(&f);
+    if (rc) return rc;
+    FDX_HIP(hipEventRecord(f->fork, st));
+    FDX_HIP(hipStreamWaitEvent(f->side, f->fork, 0));
+    FDX_WALK((21 + kWalkLongWaves - 1) / kWalkLongWaves, 256, kWalkLongWaves, f->side, split, INT32_MAX);
+    FDX_WALK((21 + kWalkShortWaves - 1) / kWalkShortWaves, 128, kWalkShortWaves, st, 0, split);
+    FDX_HIP(hipEventRecord(f->join, f->side));
+    FDX_HIP(hipStreamWaitEvent(st, f->join, 0));
+    return FDX_OK;
+#undef FDX_WALK
+#undef FDX_WALK_K
 }
 
 extern "C" int fdx_customer_windows_interleaved(const int64_t *its_d, const double *iamt_d,

@@ -21,6 +21,7 @@ FDX_LAYOUT_GROUPED = 1  # fdx_customer_layout's flags
 FDX_TERM_RUNS, FDX_TERM_COMPACT = 1, 2  # fdx_terminal_windows_grouped's flags
 FDX_ROWS_INPUT_ORDER = 1  # fdx_forest_prepare_grouped: the featurized table by input row
 FDX_ROWS_SLOT_ORDER = 2   # ... by scoring slot (coalesced; each record carries its row)
+FDX_PREP_CUST_IN_TABLE = 32  # fdx_forest_prepare_grouped: the customer columns already sit in the table
 FDX_KEY_MOD, FDX_KEY_DIV, FDX_KEY_SUB = 0, 1, 2
 FDX_SELECT_LATEST, FDX_SELECT_FIRST_IN_RANGE = 0, 1  # fdx_table_select
 MAX_WINDOWS = 8
@@ -82,6 +83,8 @@ SIGNATURES = {
     "fdx_customer_layout_workspace_size": (c_sz, [c_i64]),
     "fdx_customer_layout": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i32, c_i32, P, P, P, P, P, P, c_i64, P, P, c_sz, P]),
     "fdx_customer_windows_walk": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i32, P, P, P, P]),
+    "fdx_customer_windows_walk_strided": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i32, P, P, c_i64, P, c_i64, c_i32,
+                                                         P]),
     "fdx_customer_windows_interleaved": (ctypes.c_int, [P, P, P, P, P, c_i64, c_i64, P, c_i32, P, P, P]),
     "fdx_exclusive_scan_u32_workspace_size": (c_sz, [c_i64]),
     "fdx_exclusive_scan_u32": (ctypes.c_int, [P, c_i64, P, P]),
@@ -167,6 +170,7 @@ SIGNATURES = {
     "fdx_forest_clear_flag": (ctypes.c_int, [P, c_i64, P, c_sz, P]),
     "fdx_forest_prepare_grouped": (ctypes.c_int, [P, c_i64, c_i32, c_i32, c_i32, P, P, P, P, P, P, P, P, c_i64, c_i32,
                                                   P, c_sz, P]),
+    "fdx_forest_prepare_in_table_ok": (ctypes.c_int, [P, c_i32, c_i64]),
     "fdx_forest_traverse_perm": (ctypes.c_int, [P, c_i64, P, P, P, P, c_sz, P]),
     "fdx_forest_set_variant": (ctypes.c_int, [P, c_i32]),
     "fdx_forest_get_variant": (ctypes.c_int, [P, P]),

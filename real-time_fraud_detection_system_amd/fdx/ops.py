@@ -587,8 +587,10 @@ def customer_layout_plan_async(seg_off, n_windows: int, stream=None, alloc=None)
 
 def customer_layout_fill(plan: LayoutPlan, seg_off, cperm, gts, gamt, windows_days, stream=None,
                          alloc=None, narrow: Narrow | None = None,
-                         ts_base: torch.Tensor | None = None) -> CustomerLayout:
+                         ts_base: torch.Tensor | None = None, irow: torch.Tensor | None = None) -> CustomerLayout:
     """The second half: slots and window starts of a plan from GROUPED ts / amount (alloc: see Arena).
+    irow: where the slot -> input row index goes (int32, >= n_slots elements: a FeatureTable's row
+    column) instead of a buffer of the layout's own.
     narrow: rekey_payload(narrow=...)'s fifth output -- gts / gamt hold the form it names; ts_base: that
     re-key's pay0 (the input timestamps; row 0 is the base of the narrow seconds)."""
     _dev(seg_off, torch.int64, "seg_off"); _dev(cperm, torch.int32, "cperm")
@@ -603,7 +605,14 @@ def customer_layout_fill(plan: LayoutPlan, seg_off, cperm, gts, gamt, windows_da
     A = alloc or _fresh(dev)
     its = A("its", m, torch.int64)
     iamt = A("iamt", m, torch.float64)
-    irow = A("irow", m, torch.int32)
+    if irow is None:
+        irow = A("irow", m, torch.int32)
+    else:
+        if _dev(irow, torch.int32, "irow").numel() < m:
+            raise FdxError(f"irow holds {irow.numel()} slots < {m}")
+        irow = irow[:m]
+        if alloc is not None:  # an arena keeps its own buffer reserved (never written): a later step
+            A("irow", m, torch.int32)  # without a table then allocates nothing, as any repeated step
     starts = A("starts", W * m, torch.int32)
     if m:
         nflag, mask = (narrow.flag, narrow.mask) if narrow is not None and narrow.mask else (None, 0)
@@ -616,13 +625,29 @@ def customer_layout_fill(plan: LayoutPlan, seg_off, cperm, gts, gamt, windows_da
     return CustomerLayout(plan.sorder, plan.goff, its, iamt, irow, m, starts, tuple(windows_days))
 
 
-def customer_windows_walk(lay: CustomerLayout, seg_off, stream=None, alloc=None):
+def customer_windows_walk(lay: CustomerLayout, seg_off, stream=None, alloc=None, table=None):
     """The windows of a layout built with windows_days: (nb int32 [W, n_slots], rolling SUM
-    float64 [W, n_slots]) indexed by slot (alloc: see Arena)."""
+    float64 [W, n_slots]) indexed by slot (alloc: see Arena).
+    table: a FeatureTable of >= n_slots slots (W = 3) -- the walk stores the counts and the AVERAGES
+    (sum / nb, the row assembly's division) straight into its cust_nb / cust_avg columns and returns
+    views of them; nothing else is written (fdx_customer_windows_walk_strided)."""
     if lay.starts is None:
         raise FdxError("layout was built without window starts")
     W = len(lay.windows_days)
     dev = lay.its.device
+    if table is not None:
+        if W != 3 or table.cap < lay.n_slots:
+            raise FdxError(f"the feature table takes 3 windows and holds {table.cap} slots (W = {W}, {lay.n_slots} slots)")
+        nb, avg = table.cust_planes()
+        if alloc is not None:  # (reserved in an arena, never written: see customer_layout_fill)
+            alloc("nb", W * lay.n_slots, torch.int32)
+            alloc("sum", W * lay.n_slots, torch.float64)
+        if lay.n_slots:
+            check(_lib.load().fdx_customer_windows_walk_strided(
+                _ptr(lay.iamt), _ptr(seg_off), _ptr(lay.sorder), _ptr(lay.goff), seg_off.numel() - 1, lay.n_slots, W,
+                _ptr(lay.starts), _ptr(nb), table.cap, _ptr(avg), table.cap, 1, _s(stream)),
+                "fdx_customer_windows_walk_strided")
+        return nb[:, :lay.n_slots], avg[:, :lay.n_slots]
     A = alloc or _fresh(dev)
     nb = A("nb", W * lay.n_slots, torch.int32).view(W, lay.n_slots)
     sm = A("sum", W * lay.n_slots, torch.float64).view(W, lay.n_slots)
@@ -798,6 +823,11 @@ class Forest:
               "fdx_forest_traverse_launches")
         return k.value
 
+    def in_table_ok(self, n_windows: int, table) -> bool:
+        """Whether the row assembly can read the customer columns from `table` (a FeatureTable) in
+        place -- forest_prepare_grouped(cust_in_table=True)."""
+        return bool(_lib.load().fdx_forest_prepare_in_table_ok(self._h, int(n_windows), table.cap))
+
     def workspace_size(self, n: int) -> int:
         return int(_lib.load().fdx_forest_workspace_size(self._h, int(n)))
 
@@ -856,17 +886,23 @@ def forest_clear_flag(forest: "Forest", n: int, ws: torch.Tensor, stream=None) -
 
 def forest_prepare_grouped(forest: "Forest", flags_mode: int, cts, camt, cnb, cavg, cperm, term_inv, term_rec,
                            ws: torch.Tensor, stream=None, n=None, val_is_sum: bool = False, term_compact: bool = False,
-                           rows_out=None, flag_cleared: bool = False, index64: bool = False):
-    """cavg holds averages, or rolling sums when val_is_sum (interleaved customer path);
+                           rows_out=None, flag_cleared: bool = False, index64: bool = False,
+                           cust_in_table: bool = False):
+    """cust_in_table: rows_out (a FeatureTable) already holds cust_nb / cust_avg (averages) / row -- the
+    walk and the layout fill wrote them there (customer_windows_walk(table=), customer_layout_fill(irow=))
+    -- and the pass reads them from it instead of cnb / cavg / cperm, which are ignored
+    (FDX_PREP_CUST_IN_TABLE).  cavg holds averages, or rolling sums when val_is_sum (interleaved customer path);
     term_compact: term_rec is terminal_windows_compact's array; rows_out: the featurized table
     written by the same pass -- a FeatureRecords (by input row) or a FeatureTable (columns by
     scoring slot, capacity >= n); flag_cleared: forest_clear_flag ran on this workspace before
     (stream-ordered before this call), so the call does not clear it itself; index64: the row
     kernel's 64-bit slot arithmetic (FDX_PREP_INDEX64: what n near 2^31 takes; same results)."""
     n = cts.numel() if n is None else int(n)
-    W = cnb.shape[0]
+    W = 3 if cust_in_table else cnb.shape[0]
     opts = (1 if val_is_sum else 0) | (4 if term_compact else 0) | (8 if flag_cleared else 0) | \
-        (16 if index64 else 0)
+        (16 if index64 else 0) | (_lib.FDX_PREP_CUST_IN_TABLE if cust_in_table else 0)
+    if cust_in_table:
+        cnb = cavg = cperm = None
     out, cap, order = None, 0, 0
     if rows_out is not None:
         if not isinstance(rows_out, (FeatureRecords, FeatureTable)):
@@ -907,6 +943,15 @@ class FeatureTable:
     def __init__(self, cap_slots: int, device):
         self.cap = (int(cap_slots) + 63) // 64 * 64
         self.buf = torch.empty(78 * self.cap, dtype=torch.uint8, device=device)
+
+    def cust_planes(self):
+        """(cust_nb int32 [3, cap], cust_avg float64 [3, cap]): the planes the customer walk writes in place."""
+        c = self.cap
+        return self.buf[: 12 * c].view(torch.int32).view(3, c), self.buf[24 * c: 48 * c].view(torch.float64).view(3, c)
+
+    def row_column(self) -> torch.Tensor:
+        """row int32 [cap]: slot -> input row (the layout fill's irow, in place)."""
+        return self.buf[72 * self.cap: 76 * self.cap].view(torch.int32)
 
     def columns(self, n_slots: int = None) -> dict:
         m, c = (self.cap if n_slots is None else int(n_slots)), self.cap

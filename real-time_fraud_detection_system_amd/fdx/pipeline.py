@@ -67,6 +67,12 @@ class FraudPipeline:
     # which has no exact cents form, so on such a table every step would pay the converting pass and
     # then the wide passes (DESIGN §3 has the measurement)
     narrow_amounts = 0
+    # 1: with an ops.FeatureTable as rows_out (3 windows, the exact walk), run_fused's customer half
+    # writes its table columns in place -- the walk cust_nb and cust_avg (the division moves into its
+    # output stage), the layout fill the row index -- and the row assembly reads them there instead of
+    # copying 40 B per slot out of scratch arrays into the table.  0: the scratch arrays, as before
+    # (tools/step_ab.py measures the two -- DESIGN §4)
+    table_in_place = 1
     # how long the host polls for the layout plan's slot count before a blocking wait: the plan of
     # step k lands only after step k - 1's forest (6.6 ms at configs[1]) when steps are queued back
     # to back, and a blocking hipEventSynchronize woke up ~150 us after it (profiles/r06t trace: plan
@@ -236,6 +242,9 @@ class FraudPipeline:
                         if validate:  # (the count's copy here too, off the terminal chain)
                             rc_t = ops.KeyRangeCheck.from_count(bad[1:2], n_terminals, "terminal ids", side)
                 # customer half first (the critical path)
+                if self.table_in_place and isinstance(rows_out, ops.FeatureTable) and half.walk and not half.scan \
+                        and self.forest.in_table_ok(W, rows_out):
+                    half.table = rows_out
                 half.rekey(customer, n_customers, ts_ns, amount, bad[0:1] if validate else None, narrow=narrow)
                 # (an ops.Narrow each, or None: which form that re-key's columns took; read by tests and tools)
                 self.narrow_flags = [half.nflag, None]
@@ -281,10 +290,12 @@ class FraudPipeline:
                             ((rows_out.buf,) if rows_out is not None else ()):
                         t.record_stream(side)
                 with torch.cuda.stream(side):
+                    # (half.table: inb / isum / lay.irow are views of rows_out's columns, isum the averages)
                     ops.forest_prepare_grouped(self.forest, self.flags_mode, lay.its, lay.iamt, inb, isum, lay.irow,
-                                               None, trec, ws, side, n=lay.n_slots, val_is_sum=True,
+                                               None, trec, ws, side, n=lay.n_slots, val_is_sum=half.table is None,
                                                term_compact=compact, rows_out=rows_out, flag_cleared=overlap,
-                                               index64=bool(self.assembly_index64))
+                                               index64=bool(self.assembly_index64),
+                                               cust_in_table=half.table is not None)
                     mk("assemble_rows", side)
                     ops.forest_traverse_perm(self.forest, lay.n_slots, ws, proba, lay.irow, side)
                     mk("forest_traverse", side)
@@ -323,6 +334,9 @@ class _CustomerHalf:
         self.scan = pipe.avg_mode == "scan"
         # the two-kernel walk serves >= 3 windows; fewer use the one-pass ring kernel
         self.walk = len(pipe.windows_days) >= 3
+        # an ops.FeatureTable whose cust_nb / cust_avg / row columns the walk and the layout fill write
+        # in place (set by run_fused before rekey(); 3 windows, exact walk); None: buffers of the arena
+        self.table = None
 
     def rekey(self, customer, n_customers: int, ts_ns, amount, bad=None, what: str = "customer ids", narrow=None):
         """The re-key carries ts and amount into grouped order (narrow: ops.rekey_payload's); bad
@@ -341,13 +355,20 @@ class _CustomerHalf:
             self.checks.append(ops.KeyRangeCheck.from_count(*self.bad, self.stream))
 
     def windows(self):
-        """Layout (host-synchronising: the slot count) and windows -> (lay, nb, rolling sum), by slot."""
+        """Layout (host-synchronising: the slot count) and windows -> (lay, nb, rolling sum), by slot;
+        with self.table: views of its columns, lay.irow included, and the AVERAGE in the sum's place."""
         p, st, cseg, gts, gamt = self.pipe, self.stream, self.cseg, self.gts, self.gamt
+        tbl = self.table if self.pending is not None else None
         try:
             if self.pending is not None:
-                lay = ops.customer_layout_fill(self.pending.result(p.plan_spin_s), cseg, self.cperm, gts, gamt,
+                plan = self.pending.result(p.plan_spin_s)
+                # the fill and the walk write into the table before the assembly sees it: the slot
+                # count is checked here, before either is enqueued (the assembly's own error)
+                if tbl is not None and tbl.cap < plan.n_slots:
+                    raise ValueError(f"the feature table holds {tbl.cap} slots < {plan.n_slots}")
+                lay = ops.customer_layout_fill(plan, cseg, self.cperm, gts, gamt,
                                                p.windows_days, st, alloc=self.scope("lay"), narrow=self.nflag,
-                                               ts_base=self.ts_ns)
+                                               ts_base=self.ts_ns, irow=None if tbl is None else tbl.row_column())
             else:
                 lay = ops.customer_layout(cseg, self.cperm, gts, gamt, len(p.windows_days), st, p._slots_hint,
                                           p.windows_days if self.walk else None, grouped=True)
@@ -361,7 +382,7 @@ class _CustomerHalf:
         if self.scan:  # the windows straight from the grouped rows into the layout's slots
             inb, isum = ops.customer_windows_scan(gts, gamt, cseg, p.windows_days, lay=lay, stream=st)
         elif self.walk:
-            inb, isum = ops.customer_windows_walk(lay, cseg, st, alloc=self.scope("walk"))
+            inb, isum = ops.customer_windows_walk(lay, cseg, st, alloc=self.scope("walk"), table=tbl)
         else:
             inb, isum = ops.customer_windows_interleaved(lay, cseg, p.windows_days, st)
         self.mark("customer_walk", st)
@@ -371,7 +392,8 @@ class _CustomerHalf:
 def check_rows_out(rows_out, ts_ns: torch.Tensor) -> None:
     """rows_out of run_fused / ShardedPipeline.run, checked before anything is enqueued: an
     ops.FeatureRecords of >= n records or an ops.FeatureTable of >= n slots (the layout's slot
-    count is >= n; its exact value is checked by the assembly), on the inputs' device."""
+    count is >= n; its exact value is checked by the assembly, or -- table_in_place -- by the
+    customer half before its layout fill writes into the table), on the inputs' device."""
     if rows_out is None:
         return
     if not isinstance(rows_out, (ops.FeatureRecords, ops.FeatureTable)):
