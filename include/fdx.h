@@ -470,11 +470,25 @@ int fdx_forest_pack_rank(const fdx_forest_desc *desc, uint32_t *nodes_out, int32
  * reference's deployed RandomForestClassifier(random_state=0), model_training.ipynb:2212): 32
  * u16 threshold-rank SLOTS, feature f spanning ceil(|U_f| / 32767) consecutive slots; slot s
  * holds min(max(r_f - slot_base[s], 0), 32767).  Node (4 B): [30:16] k' | [15:11] slot |
- * [10:0] right offset; leaf 0x7FFF0000; jump 0xFFFF0000 | offset.  version = 1 or 2 (1 = the
+ * [10:0] right offset; leaf 0x7FFF0000; jump 0xFFFF0000 | offset.  version = 1, 2 or 3 (1 = the
  * fdx_forest_pack_rank layout; thr_off_out then has 17 meaningful entries of 33, slot tables 0).
- * fdx_forest_create picks v1 when the forest fits it, else v2 when <= 16 features need <= 32
- * slots, else the wide 8-byte layout.  v2 forests score through fdx_forest_predict /
- * prepare + traverse (the fused scoring-pipeline prepares need v1). */
+ * v2 forests score through fdx_forest_predict / prepare + traverse (the fused scoring-pipeline
+ * prepares need the v1 row format).
+ * Rank layout v3, "borrow" nodes (version = 3): v1's ranks, thresholds, rank rows and eligibility,
+ * another node word and node order.  Node (4 B): [31:28] slot (= feature, 0..14) | [27:16] O |
+ * [15] 0 | [14:0] threshold rank k (go left iff r <= k, as in v1).  The two children of the
+ * internal node at word p are adjacent: the right child at word p + O - 1, the left at p + O,
+ * 2 <= O <= 4095.  A tree is its root word followed by its sibling pairs in depth-first order;
+ * after a pair come the descendants of the child with the smaller subtree, then the other's (so
+ * O <= tree size / 2 + 2; a forest with a larger O is FDX_E_UNSUPPORTED and keeps v1).  A leaf is
+ * 0x00007FFF (slot 0, O = 0); there are no jump nodes and no sentinel slot: the word count is the
+ * node count and depth_out the plain tree depth.  With the row's plane word x = slot << 28 | r
+ * (r <= 0x7FFF), d = node - x (mod 2^32) has the slot bits cancelled and a borrow out of bits 14:0
+ * iff r > k, which bit 15 hands to O: d >> 16 = O - (r > k), the distance to the child -- and 0
+ * at a leaf under every rank.  leaf_value_out / missing_left_out / orig_out by word, as in v1.
+ * fdx_forest_create picks v3 when the forest fits it and some tree is deeper than one level, else
+ * v1 when the forest fits it, else v2 when <= 16 features need <= 32 slots, else the wide 8-byte
+ * layout. */
 int fdx_forest_rank_layout_size2(const fdx_forest_desc *desc, int32_t version, int64_t *n_nodes,
                                  int32_t *n_thresholds, int32_t *n_slots);
 int fdx_forest_pack_rank2(const fdx_forest_desc *desc, int32_t version, uint32_t *nodes_out, int32_t *orig_out,
@@ -490,9 +504,11 @@ int fdx_forest_pack_rank2(const fdx_forest_desc *desc, int32_t version, uint32_t
  * the trees exceed the kernel's LDS budget (the generic prepare kernel is used then). */
 int fdx_forest_search_trees(const fdx_forest_desc *desc, float *trees_out, int64_t cap, int64_t *n_floats,
                             int32_t *eoff_out /* [4] */, int32_t *elev_out /* [4] */);
-/* *layout = 0 (wide 8-byte nodes), 1 (rank v1, the default when the forest fits it), 2 (rank
+/* *layout = 0 (wide 8-byte nodes), 1 (4-byte rank nodes over the v1 row format and u32 planes:
+ * rank v3 borrow nodes, the default when the forest fits them, with *n_slots = 15, or rank v1
+ * with *n_slots = 16 -- its 15 feature slots and the sentinel slot v3 does not have), 2 (rank
  * v2) or 3 (rank v2 with one slot per feature: v1 row format, compact 32 KiB row planes);
- * *n_slots = rank slots.  fdx_forest_set_variant rebuilds the rank layout in the other node
+ * *n_slots = rank slots.  fdx_forest_set_variant rebuilds the rank layout in another node
  * format when the requested variant needs it. */
 int fdx_forest_layout(fdx_forest forest, int32_t *layout, int32_t *n_slots);
 int fdx_forest_destroy(fdx_forest forest);
@@ -526,13 +542,16 @@ int fdx_forest_traverse(fdx_forest forest, int64_t n, double *proba_d, int32_t *
 int fdx_forest_traverse_launches(fdx_forest forest, int64_t n, int32_t with_leaves, int32_t *launches);
 /* Traversal kernel shape (one default per layout):
  *   0 = wide layout (8-byte nodes, float32 rows; any forest, the only one for > 15 features),
- *   1 = rank layout v1, 1,024 threads x 10 trees per lane (the default when the forest fits v1),
+ *   1 = rank layout v1, 1,024 threads x 10 trees per lane (the default of forests that fit v1
+ *       but not v3, and of forests no deeper than one level),
  *   2 = rank layout v2, 32 threshold slots (the default for forests v1 cannot hold),
  *   3 = v2 nodes over 16 compact u16 planes (every feature in one slot),
  *   4 = rank layout v2 with 10 trees per lane,
  *   5 = rank layout v2 over paired planes: two rows per lane, only the forest's threshold slots
  *       staged (the v2 default when every tree fits the node budget left beside them: the
- *       reference's deployed RF(100, unlimited depth), 22 slots).
+ *       reference's deployed RF(100, unlimited depth), 22 slots),
+ *   6 = rank layout v3 (borrow nodes), variant 1's shape with 4 instead of 5 VALU per walk step
+ *       (the default when the forest fits v3).
  * Variants > 0 need <= 15 features (the rank rows' 16th slot is the v1 sentinel) and the
  * rank layout (FDX_E_UNSUPPORTED otherwise; a
  * refused call leaves the forest's node format, variant and chunks as they were).

@@ -197,10 +197,15 @@ __device__ __forceinline__ uint32_t lds16(const char *lds, uint32_t byte_addr) {
 // Node / plane formats (template parameter P16): 0 = u32 planes, 4-bit feature, 12-bit right
 // offset (rank layout v1); 2 = rank layout v2: u16 planes of 1,024 rows, a 5-bit SLOT field and
 // an 11-bit right offset (see build_rank_layout).
+// 5 = rank layout v3, borrow nodes over u32 planes of slot << 28 | rank (fdx_forest_internal.h):
+// the step is d = node - x, pa += 4 (d >> 16); a chain is at a leaf iff node & kBorrowOMask == 0.
 template <int P16>
-constexpr uint32_t kSlotMask = P16 >= 2 ? 0xF800u : 0xF000u;
+constexpr bool kBorrow = P16 == 5;
 template <int P16>
-constexpr uint32_t kOffMask = P16 >= 2 ? 0x7FFu : 0xFFFu;
+constexpr uint32_t kSlotMask = (P16 >= 2 && P16 <= 4) ? 0xF800u : 0xF000u;
+// the node bits that are zero at a leaf and only there (v1 / v2: the right offset)
+template <int P16>
+constexpr uint32_t kOffMask = kBorrow<P16> ? kBorrowOMask : (P16 >= 2 ? 0x7FFu : 0xFFFu);
 // 3 = the v2 node format over 16 u16 planes of 1,024 rows (32 KiB): forests whose every feature
 // fits one slot (slot = feature, the v1 row format); the node region starts at 32 KiB, so a
 // chunk holds a third more nodes than with 64 KiB of planes (fewer chunk launches per batch)
@@ -213,7 +218,7 @@ constexpr uint32_t kOffMask = P16 >= 2 ? 0x7FFu : 0xFFFu;
 // tree per chunk: with one row per lane that is ONE dependency chain per lane (latency-bound,
 // r06d PMC: 67 % of wave time in s_waitcnt); two rows double the chains in flight per CU.
 template <int P16>
-constexpr uint32_t kNodeB = P16 == 3 ? 32768u : (P16 == 4 ? 0u : kRankNodeB);
+constexpr uint32_t kNodeB = P16 == 3 ? 32768u : (P16 == 4 ? 0u : kRankNodeB);  // (v3: plane 15 stays unused)
 template <int P16>
 __device__ __forceinline__ uint32_t plane_addr(uint32_t nd, uint32_t lane_base) {
     if constexpr (P16 == 4) {
@@ -221,8 +226,18 @@ __device__ __forceinline__ uint32_t plane_addr(uint32_t nd, uint32_t lane_base) 
         uint32_t t, a;
         asm("v_and_b32 %0, 0xf800, %2\n\tv_lshl_add_u32 %1, %0, 1, %3" : "=&v"(t), "=v"(a) : "v"(nd), "v"(lane_base));
         return a;
+    } else if constexpr (kBorrow<P16>) {
+        // slot s's plane at byte 4,096 s; 2 VALU (the compiler's form: v_and_b32_sdwa on the node's
+        // high word, v_add_u32 -- r11 ISA)
+        return ((nd >> 16) & 0xF000u) | lane_base;
     } else
         return (nd & kSlotMask<P16>) | lane_base;
+}
+// pa + 4 * (d >> 16): v_mad_u32_u16 on the high half of d (O - borrow <= 4,095: no overflow)
+__device__ __forceinline__ uint32_t borrow_next(uint32_t d, uint32_t pa) {
+    uint32_t pn;
+    asm("v_mad_u32_u16 %0, %1, 4, %2 op_sel:[1,0,0,0]" : "=v"(pn) : "v"(d), "v"(pa));
+    return pn;
 }
 
 // Compact planes (P16 = 3) are read a DWORD at a time: the lane's u16 rank is the low half
@@ -239,7 +254,7 @@ __device__ __forceinline__ uint32_t plane_shift() {
 }
 template <int P16>
 __device__ __forceinline__ uint32_t rank_x(const char *lds, uint32_t addr) {
-    return P16 == 3 ? lds32(lds, addr) : (P16 ? lds16(lds, addr) : lds32(lds, addr));
+    return (P16 == 3 || kBorrow<P16>) ? lds32(lds, addr) : (P16 ? lds16(lds, addr) : lds32(lds, addr));
 }
 
 template <bool NAN_AWARE, int P16, int K>
@@ -254,6 +269,15 @@ __device__ __forceinline__ void rank_step(const char *lds, const uint32_t (&lane
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
+        if constexpr (kBorrow<P16>) {
+            if (NAN_AWARE && (x[k] & 0xFFFFu) == 0xFFFFu) {  // the NaN rank; a leaf (O = 0) stays
+                const uint32_t o = (nd[k] >> 16) & 0xFFFu;
+                pa[k] += (o == 0 ? 0u : o - (mleft[(pa[k] - kNodeB<P16>) >> 2] != 0 ? 0u : 1u)) << 2;
+            } else {
+                pa[k] = borrow_next(nd[k] - x[k], pa[k]);
+            }
+            continue;
+        }
         uint32_t st;
         if (NAN_AWARE && x[k] == (P16 ? 0xFFFFu : 0xFFFF0000u)) {  // (u32 planes: stage_planes_u32)
             st = mleft[(pa[k] - kNodeB<P16>) >> 2] != 0 ? 1u : (nd[k] & kOffMask<P16>);
@@ -315,6 +339,34 @@ __device__ __forceinline__ void il_node1(uint32_t &p0, uint32_t x0, uint32_t n0)
         : [p0] "+v"(p0), [d0] "=&v"(d0), [o0] "=&v"(o0) : [x0] "v"(x0), [n0] "v"(n0));
 }
 
+// The same for borrow nodes: d = nd - x, pa += 4 (d >> 16) -- two subs, two mads.
+__device__ __forceinline__ void il_borrow2(uint32_t &p0, uint32_t &p1, uint32_t x0, uint32_t x1, uint32_t n0, uint32_t n1) {
+    uint32_t d0, d1;
+    asm("v_sub_u32 %[d0], %[n0], %[x0]\n\tv_sub_u32 %[d1], %[n1], %[x1]\n\t"
+        "v_mad_u32_u16 %[p0], %[d0], 4, %[p0] op_sel:[1,0,0,0]\n\tv_mad_u32_u16 %[p1], %[d1], 4, %[p1] op_sel:[1,0,0,0]"
+        : [p0] "+v"(p0), [p1] "+v"(p1), [d0] "=&v"(d0), [d1] "=&v"(d1)
+        : [x0] "v"(x0), [x1] "v"(x1), [n0] "v"(n0), [n1] "v"(n1));
+}
+__device__ __forceinline__ void il_borrow1(uint32_t &p0, uint32_t x0, uint32_t n0) {
+    uint32_t d0;
+    asm("v_sub_u32 %[d0], %[n0], %[x0]\n\tv_mad_u32_u16 %[p0], %[d0], 4, %[p0] op_sel:[1,0,0,0]"
+        : [p0] "+v"(p0), [d0] "=&v"(d0) : [x0] "v"(x0), [n0] "v"(n0));
+}
+template <int P16>
+__device__ __forceinline__ void il_step2(uint32_t &p0, uint32_t &p1, uint32_t x0, uint32_t x1, uint32_t n0, uint32_t n1) {
+    if constexpr (kBorrow<P16>)
+        il_borrow2(p0, p1, x0, x1, n0, n1);
+    else
+        il_node2(p0, p1, x0, x1, n0, n1);
+}
+template <int P16>
+__device__ __forceinline__ void il_step1(uint32_t &p0, uint32_t x0, uint32_t n0) {
+    if constexpr (kBorrow<P16>)
+        il_borrow1(p0, x0, n0);
+    else
+        il_node1(p0, x0, n0);
+}
+
 template <int P16, int K, int PW>
 __device__ __forceinline__ int rank_walk_pipe(const char *lds, const uint32_t (&lane_base)[K], uint32_t (&pa)[K],
                                               uint32_t (&nd)[K], int depth, int pre = 0) {
@@ -325,23 +377,23 @@ __device__ __forceinline__ int rank_walk_pipe(const char *lds, const uint32_t (&
     for (int k = 0; k < K; ++k) x[k] = fetch_x(k);
     auto step = [&]() {
         if constexpr (PW >= 100) {
-            static_assert(PW == 102 && P16 == 0, "interleaved pairs: u32 planes");
+            static_assert(PW == 102 && (P16 == 0 || kBorrow<P16>), "interleaved pairs: u32 planes");
 #pragma unroll
             for (int g = 0; g < K; g += 2) {
                 if (g + 1 < K) {
-                    il_node2(pa[g], pa[g + 1], x[g], x[g + 1], nd[g], nd[g + 1]);
+                    il_step2<P16>(pa[g], pa[g + 1], x[g], x[g + 1], nd[g], nd[g + 1]);
                     nd[g + 1] = lds32(lds, pa[g + 1]);
                     nd[g] = lds32(lds, pa[g]);
                 } else {
-                    il_node1(pa[g], x[g], nd[g]);
+                    il_step1<P16>(pa[g], x[g], nd[g]);
                     nd[g] = lds32(lds, pa[g]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
             for (int g = 0; g < K; g += 2) {
-                const uint32_t a0 = (nd[g] & kSlotMask<P16>) | lane_base[g];
-                const uint32_t a1 = g + 1 < K ? (nd[g + 1] & kSlotMask<P16>) | lane_base[g + 1] : 0u;
+                const uint32_t a0 = plane_addr<P16>(nd[g], lane_base[g]);
+                const uint32_t a1 = g + 1 < K ? plane_addr<P16>(nd[g + 1], lane_base[g + 1]) : 0u;
                 x[g] = rank_x<P16>(lds, a0);
                 if (g + 1 < K) x[g + 1] = rank_x<P16>(lds, a1);
                 __builtin_amdgcn_sched_barrier(0);
@@ -380,9 +432,9 @@ __device__ __forceinline__ int rank_walk_pipe(const char *lds, const uint32_t (&
 #pragma unroll
             for (int g = 0; g < K; g += 2) {
                 if (g + 1 < K)
-                    il_node2(pa[g], pa[g + 1], x[g], x[g + 1], nd[g], nd[g + 1]);
+                    il_step2<P16>(pa[g], pa[g + 1], x[g], x[g + 1], nd[g], nd[g + 1]);
                 else
-                    il_node1(pa[g], x[g], nd[g]);
+                    il_step1<P16>(pa[g], x[g], nd[g]);
             }
         } else {
 #pragma unroll
@@ -477,9 +529,21 @@ __device__ __forceinline__ int rank_trees_from(const char *lds, const uint32_t (
 #pragma unroll
         for (int g = 0; g < GG; ++g)
 #pragma unroll
-            for (int r = 0; r < R; ++r) x[r * GG + g] = lds32(lds, (rn[g] & 0xF000u) | lane_base[r * GG + g]);
+            for (int r = 0; r < R; ++r)
+                x[r * GG + g] = lds32(lds, plane_addr<P16>(rn[g], lane_base[r * GG + g]));  // (slot bits: SALU)
 #pragma unroll
         for (int g = 0; g < GG; ++g) {
+            if constexpr (kBorrow<P16>) {  // d = root - x, pa = root address + 4 (d >> 16): 2 VALU
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int k = r * GG + g;
+                    uint32_t dd;
+                    asm("v_sub_u32 %[d], %[n], %[x]\n\t"
+                        "v_mad_u32_u16 %[p], %[d], 4, %[b] op_sel:[1,0,0,0]"
+                        : [p] "=v"(pa[k]), [d] "=&v"(dd) : [x] "v"(x[k]), [n] "s"(rn[g]), [b] "s"(rp[g]));
+                }
+                continue;
+            }
             const uint32_t off = __builtin_amdgcn_readfirstlane(rn[g] & 0xFFFu);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -624,11 +688,17 @@ __device__ __forceinline__ void stage_words(uint32_t *s_x, int r, const uint32_t
 // 0xFFFF0000, the NaN-aware walk's marker (ranks are <= 0x7FFF): no second form for NaN batches
 // (a form per batch kind left the compiler computing one and moving it into the other's
 // registers, 15 v_mov per tile).
-template <int BLOCK>
+// Borrow nodes: the plane word is slot << 28 | rank (NaN: the low half 0xFFFF, the marker).
+template <int BLOCK, int P16>
 __device__ __forceinline__ void stage_planes_u32(uint32_t *s_x, int r, const uint32_t (&w)[8]) {
     uint32_t x[15];
 #pragma unroll
-    for (int f = 0; f < 15; ++f) x[f] = (f & 1) ? w[f >> 1] & 0xFFFF0000u : w[f >> 1] << 16;
+    for (int f = 0; f < 15; ++f) {
+        if constexpr (kBorrow<P16>)
+            x[f] = ((f & 1) ? w[f >> 1] >> 16 : w[f >> 1] & 0xFFFFu) | ((uint32_t)f << 28);
+        else
+            x[f] = (f & 1) ? w[f >> 1] & 0xFFFF0000u : w[f >> 1] << 16;
+    }
     stage_words<BLOCK>(s_x, r, x);
 }
 
@@ -652,6 +722,8 @@ __global__ void __launch_bounds__(BLOCK, 1) k_forest_rank(
     constexpr int kXW = P16 == 3 ? kRankXWords / 2 : kRankXWords;  // row-plane words in LDS (below the nodes)
     constexpr int kNodeW0 = P16 == 4 ? 0 : kXW;                    // first node word
     constexpr uint32_t kNB = kNodeB<P16>;
+    constexpr bool kFlipK = P16 >= 2 && P16 <= 4;  // u16 planes: the LDS copy of a node is node ^ 0xFFFF0000
+    constexpr bool kU32 = P16 == 0 || kBorrow<P16>;  // u32 planes, one row per lane, natural order
     static_assert(P16 != 4 || (R == 2 && BLOCK == kPlaneRows), "paired planes: two rows per lane, 1,024 lanes");
     // paired planes: plane s at byte pb + 4,096 s (uniform)
     const uint32_t pb = P16 == 4 ? (uint32_t)(kLdsTotal - 4096 * n_slots) & ~15u : 0u;
@@ -694,11 +766,11 @@ __global__ void __launch_bounds__(BLOCK, 1) k_forest_rank(
                 for (int j = 0; j < 4; ++j) v[j] = nb[min(i0 + j * BLOCK, chunk_nodes - 1)];  // (clamped: no branch)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (i0 + j * BLOCK < chunk_nodes) s_mem[kNodeW0 + i0 + j * BLOCK] = P16 ? v[j] ^ 0xFFFF0000u : v[j];
+                    if (i0 + j * BLOCK < chunk_nodes) s_mem[kNodeW0 + i0 + j * BLOCK] = kFlipK ? v[j] ^ 0xFFFF0000u : v[j];
             }
         } else {  // several loads in flight: with one tile per block (small batches) the fill is a
                   // large share of a block's work (rolled: stream micro-batches +8 us, r05bp)
-            for (int i = tid; i < chunk_nodes; i += BLOCK) s_mem[kNodeW0 + i] = P16 ? nb[i] ^ 0xFFFF0000u : nb[i];
+            for (int i = tid; i < chunk_nodes; i += BLOCK) s_mem[kNodeW0 + i] = kFlipK ? nb[i] ^ 0xFFFF0000u : nb[i];
         }
     };
     fill_nodes();
@@ -721,7 +793,7 @@ __global__ void __launch_bounds__(BLOCK, 1) k_forest_rank(
 #pragma unroll
     for (int r = 0; r < R; ++r)  // compact planes: the byte address of the dword holding the lane's u16
         lrow[r] = P16 == 4 ? pb + (uint32_t)tid * 4u + 2u * r
-                           : (uint32_t)(P16 == 3 ? ((r * BLOCK + pslot) & ~1) * 2 : (r * BLOCK + pslot) * (P16 ? 2 : 4));
+                           : (uint32_t)(P16 == 3 ? ((r * BLOCK + pslot) & ~1) * 2 : (r * BLOCK + pslot) * (kU32 ? 4 : 2));
     // paired planes: the lane's two rank rows (32 u16 slots each, as q0..q3 hold them) as n_slots
     // dwords, row 0 in the low halves
     auto stage_paired = [&](const uint4 (&a0)[R], const uint4 (&a1)[R], const uint4 (&a2)[R], const uint4 (&a3)[R]) {
@@ -873,8 +945,8 @@ __global__ void __launch_bounds__(BLOCK, 1) k_forest_rank(
                         s_x16[f * kPlaneRows + r * BLOCK + pslot] = (uint16_t)((w16[f >> 1] >> ((f & 1) * 16)) & 0xFFFFu);
                 } else {
                     const uint32_t w8[8] = {q0[r].x, q0[r].y, q0[r].z, q0[r].w, q1[r].x, q1[r].y, q1[r].z, q1[r].w};
-                    if constexpr (P16 == 0) {
-                        stage_planes_u32<BLOCK>(s_x, r, w8);
+                    if constexpr (kU32) {
+                        stage_planes_u32<BLOCK, P16>(s_x, r, w8);
                     } else {
 #pragma unroll
                         for (int f = 0; f < 16; ++f)
@@ -969,8 +1041,8 @@ __global__ void __launch_bounds__(BLOCK, 1) k_forest_rank(
                     s_x16[f * kPlaneRows + r * BLOCK + pslot] = (uint16_t)((w[f >> 1] >> ((f & 1) * 16)) & 0xFFFFu);
             } else {
                 const uint32_t w[8] = {q0[r].x, q0[r].y, q0[r].z, q0[r].w, q1[r].x, q1[r].y, q1[r].z, q1[r].w};
-                if constexpr (P16 == 0) {
-                    stage_planes_u32<BLOCK>(s_x, r, w);
+                if constexpr (kU32) {
+                    stage_planes_u32<BLOCK, P16>(s_x, r, w);
                 } else {
 #pragma unroll
                     for (int f = 0; f < 16; ++f)
@@ -1042,10 +1114,10 @@ using namespace fdx;
 
 namespace fdx {
 namespace {
-int install_rank_layout(fdx_forest_s *F, bool v2, hipStream_t st);
-// node format a variant runs on: 1 = rank layout v1, 2 = v2
-int variant_format(const Variant &v) { return v.p16 >= 2 ? 2 : 1; }
-int forest_format(const fdx_forest_s *F) { return F->rank_v2 ? 2 : 1; }
+int install_rank_layout(fdx_forest_s *F, int format, hipStream_t st);
+// node format a variant runs on: 1 = rank layout v1, 2 = v2, 3 = v3 (borrow nodes)
+int variant_format(const Variant &v) { return v.p16 == 5 ? 3 : (v.p16 >= 2 ? 2 : 1); }
+int forest_format(const fdx_forest_s *F) { return F->rank_borrow ? 3 : (F->rank_v2 ? 2 : 1); }
 int variant_group(const fdx_forest_s *F) { return F->zstride == 16 ? kVariants[F->variant].group : 4; }
 
 
@@ -1130,7 +1202,8 @@ extern "C" int fdx_forest_set_variant(fdx_forest F, int32_t variant) {
     // every failure below leaves the forest exactly as it was: the previous node format (the
     // rank layout is rebuilt in it when it was switched), the previous variant and its chunks
     auto refuse = [&](const char *why, int a) {
-        if (forest_format(F) != had) install_rank_layout(F, had == 2, nullptr);
+        // (a failed install leaves no rank layout at all: rank_ok is false then)
+        if (!F->rank_ok || forest_format(F) != had) install_rank_layout(F, had, nullptr);
         F->variant = prev;
         build_chunks(F);
         upload_chunks(F);
@@ -1138,7 +1211,7 @@ extern "C" int fdx_forest_set_variant(fdx_forest F, int32_t variant) {
         return FDX_E_UNSUPPORTED;
     };
     if (v.rank && variant_format(v) != had) {  // the variant runs on the other node format
-        if (install_rank_layout(F, variant_format(v) == 2, nullptr))
+        if (install_rank_layout(F, variant_format(v), nullptr))
             return refuse("variant %d needs rank layout v%d, which this forest does not fit", variant_format(v));
     }
     if (v.rank && v.p16 == 3 && !F->rank_identity)
@@ -1161,7 +1234,8 @@ extern "C" int fdx_forest_get_variant(fdx_forest F, int32_t *variant) {
 extern "C" int fdx_forest_layout(fdx_forest F, int32_t *layout, int32_t *n_slots) {
     FDX_REQUIRE(F && layout && n_slots, "null pointer");
     *layout = !F->rank_ok ? 0 : (F->rank_v2 ? (F->rank_identity ? 3 : 2) : 1);
-    *n_slots = F->rank_v2 ? F->rn_slots : (F->rank_ok ? 16 : 0);
+    // (v1 rows: 15 feature slots + v1's sentinel slot; v3 borrow nodes have no sentinel)
+    *n_slots = F->rank_v2 ? F->rn_slots : (F->rank_ok ? (F->rank_borrow ? 15 : 16) : 0);
     return FDX_OK;
 }
 
@@ -1178,22 +1252,25 @@ void free_rank_buffers(fdx_forest_s *F) {
     }
 }
 
-// Build the rank layout (v2 nodes when `v2`, else v1) from the host copy of the packed forest
+// Build the rank layout (node format 1, 2 or 3: v3 shares v1's ranks, rows and tables) from the host
+// copy of the packed forest
 // and upload it with its search tables; synchronous (creation / set_variant, off the hot path).
 // On FDX_E_UNSUPPORTED the forest has no rank layout (rank_ok = false).
-int install_rank_layout(fdx_forest_s *F, bool v2, hipStream_t st) {
+int install_rank_layout(fdx_forest_s *F, int format, hipStream_t st) {
+    const bool v2 = format == 2;
     free_rank_buffers(F);
-    F->rank_ok = F->rank_v2 = F->rank_identity = false;
+    F->rank_ok = F->rank_v2 = F->rank_identity = F->rank_borrow = false;
     fdx_forest_desc d{};
     d.n_trees = F->n_trees;
     d.n_features = F->n_features;
     d.node_offsets = F->node_offsets.data();
     RankLayout RL;
     if (v2 && F->zstride != 16) return FDX_E_UNSUPPORTED;
-    int rc = build_rank_layout(&d, F->h_packed, F->h_orig, F->h_depth, kRankNodeCap, RL, v2);
+    int rc = build_rank_layout(&d, F->h_packed, F->h_orig, F->h_depth, kRankNodeCap, RL, format);
     if (rc) return rc;
     F->rank_ok = true;
     F->rank_v2 = v2;
+    F->rank_borrow = format == 3;
     if (v2) {
         bool ident = RL.n_slots <= 16 && RL.n_slots == F->n_features;
         for (int j = 0; j < RL.n_slots && ident; ++j) ident = RL.slot_feat[j] == j && RL.slot_base[j] == 0;
@@ -1332,13 +1409,15 @@ extern "C" int fdx_forest_create(const fdx_forest_desc *d, fdx_forest *out, void
             return fail(e, "hipDeviceGetAttribute");
         if (ncu > 0) F->n_cu = ncu;
     }
-    // Rank layout choice: v1 when the forest fits it (measured fastest on MI355X for the bench
-    // model: 8.06 vs 8.68 ms for the compact v2 planes, profiles/r02_v6_ab_*.json); else v2 (more
-    // than 4,096 nodes under one threshold rank or ranks past 12 bits -- the deployed model);
-    // else the wide 8-byte layout.  (fdx_forest_set_variant switches an existing forest to the
-    // other rank format.)
-    rc = install_rank_layout(F, false, st);
-    if (rc == FDX_E_UNSUPPORTED) rc = install_rank_layout(F, true, st);
+    // Rank layout choice: v3 (borrow nodes: one VALU less per walk step than v1, step 9.69 -> 9.10
+    // ms, profiles/r11_borrow_walk_ab.txt) when the forest fits it and has a steady-state step to
+    // gain from (some tree deeper than one level); else v1 when the forest fits it (8.06 vs 8.68 ms
+    // for the compact v2 planes, profiles/r02_v6_ab_*.json); else v2 (features with more than
+    // 32,767 thresholds -- the deployed model); else the wide 8-byte layout.
+    // (fdx_forest_set_variant switches an existing forest to another rank format.)
+    rc = *std::max_element(depth.begin(), depth.end()) >= 2 ? install_rank_layout(F, 3, st) : FDX_E_UNSUPPORTED;
+    if (rc == FDX_E_UNSUPPORTED) rc = install_rank_layout(F, 1, st);
+    if (rc == FDX_E_UNSUPPORTED) rc = install_rank_layout(F, 2, st);
     if (rc == FDX_E_UNSUPPORTED) rc = FDX_OK;  // the wide layout serves it
     if (rc) {
         fdx_forest_destroy(F);
@@ -1347,7 +1426,7 @@ extern "C" int fdx_forest_create(const fdx_forest_desc *d, fdx_forest *out, void
     set_error("");
     // default kernel: the rank layout when the forest fits it, else the wide layout
     F->variant = !F->rank_ok ? 0
-                             : (!F->rank_v2 ? kDefaultRankVariant
+                             : (!F->rank_v2 ? (F->rank_borrow ? kBorrowRankVariant : kDefaultRankVariant)
                                             : (F->rank_identity ? kDefaultRankCompactVariant : kDefaultRankV2Variant));
     if (F->variant == kDefaultRankV2Variant) {
         // paired planes when every tree fits below the forest's slot planes: the deployed model
@@ -1567,6 +1646,7 @@ static int forest_traverse(fdx_forest F, int64_t n, double *proba_d, const int32
                 case 3: FDX_LAUNCH_RANK(1024, 1, 6, 3, 2); break;
                 case 4: FDX_LAUNCH_RANK(1024, 1, 10, 2, 2); break;
                 case 5: FDX_LAUNCH_RANK(1024, 2, 2, 4, 2); break;
+                case 6: FDX_LAUNCH_RANK(1024, 1, 10, 5, 102); break;
                 default: FDX_LAUNCH_RANK(1024, 1, 10, 0, 102); break;
             }
 #undef FDX_LAUNCH_RANK

@@ -53,6 +53,7 @@ struct fdx_forest_s {
     // rank layout v2 (32 threshold-rank slots, see build_rank_layout)
     bool rank_v2 = false;
     bool rank_identity = false;  // v2 with slot s = feature s (<= 16 slots): v1 rank rows, compact planes
+    bool rank_borrow = false;    // rank layout v3 (sibling-pair "borrow" nodes; v1 rank rows and tables)
     // host copies of the packed forest and scaler (set_variant rebuilds the rank layout in the
     // other node format when a variant needs it)
     std::vector<uint64_t> h_packed;
@@ -94,6 +95,18 @@ constexpr uint32_t kRankSentinel = 0x4000u << 16;
 constexpr int kRankMaxOffset = 4095;
 constexpr int kRankMaxRank = 32766;  // rank values stay <= 0x7FFF so x < 2^31
 constexpr int kRankPlaneRows = 1024;
+// Rank layout v3, "borrow" nodes (same ranks, rank rows and search tables as v1; include/fdx.h has
+// the format): node = slot << 28 | O << 16 | k, the children of the node at word p are the
+// adjacent words p + O - 1 (right) and p + O (left), and a row's plane word for slot s is
+// s << 28 | r.  Then d = node - x has the slot bits cancelled and a borrow out of the low half
+// iff r > k, which bit 15 (0 in both) passes into O (>= 2, so it ends there):
+//   d >> 16 = O - (r > k)            next address = addr + 4 * (d >> 16)   (v_sub, v_mad_u32_u16)
+//   rank address = ((node >> 16) & 0xF000) | lane_base                    (shift, v_and_or)
+// 4 VALU + 2 LDS reads per step against v1's 5 + 2.  A leaf (slot 0, O 0, k 0x7FFF) has d >> 16
+// = 0 under every rank: a fixed point with no sentinel plane, and no jump nodes exist.
+constexpr uint32_t kBorrowLeaf = 0x00007FFFu;
+constexpr uint32_t kBorrowOMask = 0x0FFF0000u;  // zero iff leaf
+constexpr int kBorrowMaxO = 4095;
 constexpr int kRankXWords = 16 * kRankPlaneRows;  // 64 KiB of row planes
 
 struct RankTab {
@@ -138,19 +151,21 @@ constexpr int kRatN = 128;             // ratio rank table: nb, fr < kRatN (32 K
 // per lane, G trees walked at once per lane (G independent LDS dependency chains), the
 // software-pipelined walk with waits grouped by PIPE chains.  p16 = the rank node / plane
 // format: 0 = v1 (u32 planes), 2 = v2 (32 threshold slots over u16 planes), 3 = v2 nodes over
-// 16 u16 planes (forests whose every feature fits one slot).
+// 16 u16 planes (forests whose every feature fits one slot), 5 = v3 borrow nodes (u32 planes).
 struct Variant {
     int block, rows, group, rank, p16, pipe;
 };
 constexpr Variant kVariants[] = {
     {512, 1, 4, 0, 0, 0},    // 0: wide layout
-    {1024, 1, 10, 1, 0, 102},  // 1: rank layout v1, 10 chains per lane (the default: r03 sweep, 7.63 vs
+    {1024, 1, 10, 1, 0, 102},  // 1: rank layout v1, 10 chains per lane (v1's default: r03 sweep, 7.63 vs
                                //    8.43 ms for 6 chains at config 2; 12 chains spill, 11.7 ms), each
                                //    step's VALU interleaved over chain pairs (r05: 6.51 -> 6.43 ms)
     {1024, 1, 6, 1, 2, 2},   // 2: rank layout v2 (forests v1 cannot hold: the deployed model)
     {1024, 1, 6, 1, 3, 2},   // 3: v2 nodes over 16 u16 planes (a third more nodes per LDS chunk)
     {1024, 1, 10, 1, 2, 2},  // 4: v2, 10 chains
     {1024, 2, 2, 1, 4, 2},   // 5: v2 over paired planes (two rows per lane, the forest's slots only)
+    {1024, 1, 10, 1, 5, 102},  // 6: rank layout v3 (borrow nodes), otherwise variant 1's shape (the default
+                               //    when the forest fits v3: traverse 6.45 -> 5.84 ms, r11)
 };
 // the variant's rank rows in HBM are v2's 32 u16 slots (64 B)
 constexpr bool v2_rows(int p16) { return p16 == 2 || p16 == 4; }
@@ -175,6 +190,7 @@ constexpr int kDefaultRankVariant = 1;
 constexpr int kDefaultRankV2Variant = 2;
 constexpr int kDefaultRankCompactVariant = 3;
 constexpr int kPairedRankV2Variant = 5;  // the v2 default when every tree fits its node budget
+constexpr int kBorrowRankVariant = 6;
 // trees per chunk the one-launch chunk loop walks as one group: the bench forest's chunks hold <= 6
 // (3.9k-node trees in 94 KiB), and the loop instantiated for 7-8 as well spilled 17 VGPRs
 constexpr int kClMaxTrees = 6;
@@ -220,6 +236,6 @@ constexpr int64_t kSlotSpan = 32767;  // thresholds per rank-layout-v2 slot (bui
 void build_search_trees(const RankLayout &L, std::vector<float> &trees, int32_t eoff[4], int32_t elev[4]);
 int build_rank_layout(const fdx_forest_desc *d, const std::vector<uint64_t> &packed,
                       const std::vector<int32_t> &worig, const std::vector<int32_t> &wdepth, int64_t max_tree_nodes,
-                      RankLayout &L, bool v2 = false);
+                      RankLayout &L, int version = 1);  // 1, 2 or 3 (borrow nodes)
 
 }  // namespace fdx

@@ -110,6 +110,64 @@ int pack_forest(const fdx_forest_desc *d, std::vector<uint64_t> &packed, std::ve
 
 
 
+// Rank layout v3: a tree is its root word followed by its sibling pairs in depth-first order
+// (right child, then left: the words p + O - 1 and p + O of the parent at p); after a pair come the
+// descendants of the child with the smaller subtree, then the other's, so O <= size / 2 + 2.
+// Leaf values, missing_left and orig by word; depth is the plain tree depth (no jump nodes).
+static int emit_borrow(const fdx_forest_desc *d, const std::vector<uint64_t> &packed,
+                       const std::vector<int32_t> &worig, const std::vector<int32_t> &wdepth, int64_t max_tree_nodes,
+                       const std::vector<std::vector<float>> &U, RankLayout &L) {
+    int64_t worst = 0;
+    // wide node w, the root of a subtree of `size` nodes, goes to the (already reserved) word p
+    std::function<void(int64_t, int64_t, int64_t)> place = [&](int64_t p, int64_t w, int64_t size) {
+        const uint64_t nd = packed[(size_t)w];
+        L.orig[(size_t)p] = worig[(size_t)w];
+        if (!(nd >> 63)) {
+            memcpy(&L.lval[(size_t)p], &nd, 8);
+            L.nodes[(size_t)p] = kBorrowLeaf;
+            return;
+        }
+        const uint32_t hi = (uint32_t)(nd >> 32), lo = (uint32_t)nd;
+        const uint32_t f = (hi >> 24) & 63;
+        float t;
+        memcpy(&t, &lo, 4);
+        const auto &u = U[f];
+        const uint32_t k = (uint32_t)(std::lower_bound(u.begin(), u.end(), t) - u.begin());
+        const int64_t q = (int64_t)L.nodes.size(), O = q + 1 - p;  // the pair: right at q, left at q + 1
+        worst = std::max(worst, O);
+        L.nodes.resize((size_t)q + 2, 0); L.orig.resize((size_t)q + 2, 0);
+        L.lval.resize((size_t)q + 2, 0.0); L.ml.resize((size_t)q + 2, 0);
+        L.nodes[(size_t)p] = (f << 28) | ((uint32_t)(O & 0xFFF) << 16) | k;
+        L.ml[(size_t)p] = (uint8_t)((hi >> 30) & 1);
+        const int64_t wl = w + 1, wr = w + (int64_t)((hi & 0xFFFFFFu) >> 3), sl = wr - wl, sr = size - 1 - sl;
+        if (sl <= sr) {
+            place(q + 1, wl, sl);
+            place(q, wr, sr);
+        } else {
+            place(q, wr, sr);
+            place(q + 1, wl, sl);
+        }
+    };
+    for (int32_t tr = 0; tr < d->n_trees; ++tr) {
+        const int64_t tb = (int64_t)L.nodes.size(), cnt = d->node_offsets[tr + 1] - d->node_offsets[tr];
+        if (cnt > max_tree_nodes) {
+            set_error("rank layout: tree %d has %lld nodes > LDS budget %lld", tr, (long long)cnt,
+                      (long long)max_tree_nodes);
+            return FDX_E_UNSUPPORTED;
+        }
+        L.nodes.push_back(0); L.orig.push_back(0); L.lval.push_back(0.0); L.ml.push_back(0);
+        place(tb, d->node_offsets[tr], cnt);
+        if (worst > kBorrowMaxO) {
+            set_error("rank layout v3: tree %d: child offset %lld > %d", tr, (long long)worst, kBorrowMaxO);
+            return FDX_E_UNSUPPORTED;
+        }
+        L.root.push_back((int32_t)tb);
+        L.depth.push_back(wdepth[(size_t)tr]);
+        L.offsets.push_back((int64_t)L.nodes.size());
+    }
+    return FDX_OK;
+}
+
 // Returns FDX_OK, or FDX_E_UNSUPPORTED (with the reason in fdx_last_error) when the forest
 // does not fit the layout (> 15 features, > 32767 distinct thresholds of one feature, a
 // tree larger than the LDS node budget).  `max_tree_nodes` = LDS node budget per chunk.
@@ -124,9 +182,12 @@ int pack_forest(const fdx_forest_desc *d, std::vector<uint64_t> &packed, std::ve
 // slot | [10:0] right offset; leaf 0x7FFF0000 (k' = 0x7FFF >= every r_j: a fixed point of
 // the u16-plane step); jump 0xFFFF0000 | offset (k' = -1 in the step's 16-bit arithmetic:
 // always right).  No sentinel slot.
+// v3 (borrow nodes, fdx_forest_internal.h): v1's ranks and eligibility, every O <= kBorrowMaxO;
+// built by emit_borrow below.
 int build_rank_layout(const fdx_forest_desc *d, const std::vector<uint64_t> &packed,
                       const std::vector<int32_t> &worig, const std::vector<int32_t> &wdepth, int64_t max_tree_nodes,
-                      RankLayout &L, bool v2) {
+                      RankLayout &L, int version) {
+    const bool v2 = version == 2;
     if (!v2 && d->n_features > 15) {
         set_error("rank layout: %d features > 15", d->n_features);
         return FDX_E_UNSUPPORTED;
@@ -175,6 +236,7 @@ int build_rank_layout(const fdx_forest_desc *d, const std::vector<uint64_t> &pac
     L.thr_off[nfeat] = (int32_t)L.thr.size();
     L.nodes.clear(); L.orig.clear(); L.lval.clear(); L.ml.clear(); L.root.clear(); L.depth.clear();
     L.offsets.assign(1, 0);
+    if (version == 3) return emit_borrow(d, packed, worig, wdepth, max_tree_nodes, U, L);
     struct Pend { int64_t owner; };
     std::vector<Pend> pend;
     int margin = 0;
@@ -327,13 +389,13 @@ static int rank_layout_host(const fdx_forest_desc *d, RankLayout &RL, int versio
     std::vector<int32_t> orig, root, depth;
     int rc = pack_forest(d, packed, orig, root, depth);
     if (rc) return rc;
-    return build_rank_layout(d, packed, orig, depth, kRankNodeCap, RL, version == 2);
+    return build_rank_layout(d, packed, orig, depth, kRankNodeCap, RL, version);
 }
 
 extern "C" int fdx_forest_rank_layout_size2(const fdx_forest_desc *d, int32_t version, int64_t *n_nodes,
                                             int32_t *n_thresholds, int32_t *n_slots) {
     FDX_REQUIRE(n_nodes && n_thresholds && n_slots, "null output");
-    FDX_REQUIRE(version == 1 || version == 2, "version must be 1 or 2");
+    FDX_REQUIRE(version >= 1 && version <= 3, "version must be 1, 2 or 3");
     RankLayout RL;
     int rc = rank_layout_host(d, RL, version);
     if (rc) return rc;
@@ -347,7 +409,7 @@ extern "C" int fdx_forest_pack_rank2(const fdx_forest_desc *d, int32_t version, 
                                      int32_t *orig_out, double *leaf_value_out, uint8_t *missing_left_out,
                                      int32_t *root_out, int32_t *depth_out, float *thr_out, int32_t *thr_off_out,
                                      int32_t *slot_feat_out, int32_t *slot_base_out) {
-    FDX_REQUIRE(version == 1 || version == 2, "version must be 1 or 2");
+    FDX_REQUIRE(version >= 1 && version <= 3, "version must be 1, 2 or 3");
     FDX_REQUIRE(nodes_out && orig_out && leaf_value_out && missing_left_out && root_out && depth_out && thr_off_out &&
                     slot_feat_out && slot_base_out,
                 "null output");

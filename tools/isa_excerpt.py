@@ -7,7 +7,9 @@ assembly, takes the default kernel (k_forest_rank<1024, 1, 10, 0, 102>), and pri
   * the text of the steady-state block of the chunk size the bench runs most (6 trees:
     the one-group loop, 6 chains in 3 interleaved pairs, 4 unrolled steps per exit test).
 
-usage: python3 tools/isa_excerpt.py [out.txt] [v2]
+usage: python3 tools/isa_excerpt.py [out.txt] [v2|v3]
+  v3: the borrow-node instantiation (k_forest_rank<1024, 1, 10, 5, 102, true>, variant 6, the
+      default for forests that fit rank layout v3): one v_mad_u32_u16 per chain-step
   v2: the rank-layout-v2 chunk-loop instantiation the deployed model runs
       (k_forest_rank<1024, 2, 2, 4, 2, true>: paired planes, one-tree chunks, two rows per lane)
 """
@@ -23,6 +25,9 @@ KERNEL = "k_forest_rankILi1024ELi1ELi10ELi0ELi102ELb1E"  # the chunk-loop instan
 
 
 KERNEL_V2 = "k_forest_rankILi1024ELi2ELi2ELi4ELi2ELb1E"  # variant 5 (paired planes), the deployed default since r06
+
+
+KERNEL_V3 = "k_forest_rankILi1024ELi1ELi10ELi5ELi102ELb1E"  # variant 6 (borrow nodes)
 
 
 def kernel_body(asm):
@@ -68,8 +73,12 @@ def main():
     global KERNEL
     out = sys.argv[1] if len(sys.argv) > 1 else None
     v2 = len(sys.argv) > 2 and sys.argv[2] == "v2"
+    v3 = len(sys.argv) > 2 and sys.argv[2] == "v3"
+    step_op = "v_mad_u32_u16" if v3 else "v_med3_i32"
     if v2:
         KERNEL = KERNEL_V2
+    if v3:
+        KERNEL = KERNEL_V3
     asm_path = "/tmp/fdx_forest_isa.s"
     subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                            "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S", "-o", asm_path,
@@ -77,16 +86,17 @@ def main():
     asm = open(asm_path).read()
     body, summ = kernel_body(asm)
     res = [("k_forest_rank<1024, 2, 2, 4, 2, true> (variant 5, rank layout v2 over paired planes: the deployed model; chunk loop)" if v2 else
-            "k_forest_rank<1024, 1, 10, 0, 102, true> (default variant 1, chunk loop)") + ", gfx950, hipcc -O3",
+            "k_forest_rank<1024, 1, 10, 5, 102, true> (variant 6, rank layout v3 borrow nodes, chunk loop)" if v3 else
+            "k_forest_rank<1024, 1, 10, 0, 102, true> (variant 1, chunk loop)") + ", gfx950, hipcc -O3",
            "register summary:"]
     res += ["  " + s for s in summ]
     res.append("")
-    res.append("walk blocks (one v_med3_i32 per chain-step): per chain-step instruction counts")
+    res.append(f"walk blocks (one {step_op} per chain-step): per chain-step instruction counts")
     res.append(f"{'block':>14} {'steps':>5} {'ds_read':>7} {'VALU':>5} {'SALU':>5} {'waitcnt':>7} {'lgkm waits':<40}")
     walk = []
     for name, b in blocks(body):
         o = ops(b)
-        n = sum(1 for x in o if x.startswith("v_med3_i32"))
+        n = sum(1 for x in o if x.startswith(step_op))
         if n < (1 if v2 else 4):
             continue
         c = collections.Counter(x.split()[0] for x in o)
