@@ -15,7 +15,11 @@ range, each micro-batch split by customer owner, terminals owned by id % N, one 
 all-to-all there and back per batch (fdx.streaming.ShardedStreamScorer); the batch latency
 is the max over ranks.  Rank 0 prints one JSON line.
 
-usage: python bench_stream.py [--gpus N] [--batches K] [--warmup W]
+--fraud-reports: the rows arrive unlabelled, as from the CDC topic, and the labels as delayed
+fraud reports before each batch (StreamScorer.report_frauds); the line gains the report call's
+device time and the five report outcomes.
+
+usage: python bench_stream.py [--gpus N] [--batches K] [--warmup W] [--fraud-reports]
 """
 import argparse
 import json
@@ -98,6 +102,10 @@ def parse(argv=None):
                     help="timed batches arrive as Debezium wire columns (decimal bytes, us timestamps, Kafka "
                          "timestamps, 2%% stale duplicate updates): device decode + dedup + compact + score "
                          "(StreamScorer.score_cdc; world 1)")
+    ap.add_argument("--fraud-reports", action="store_true",
+                    help="rows are fed unlabelled (fraud=None); before each batch the fraud reports due by then "
+                         "(the generator's labels, 3 days after the transaction) go in through "
+                         "StreamScorer.report_frauds, timed on their own (world 1, not with --cdc)")
     return ap.parse_args(argv)
 
 
@@ -210,6 +218,32 @@ def main():
                           terminal_ring=args.terminal_ring, max_batch=cap)
     cols = [("ts", torch.int64), ("customer", torch.int32), ("amount", torch.float64), ("terminal", torch.int32),
             ("fraud", torch.uint8)]
+    reports = None
+    if args.fraud_reports:
+        if world > 1 or args.cdc:
+            raise SystemExit("--fraud-reports runs at world 1 without --cdc (StreamScorer.report_frauds)")
+        # a chargeback feed: every fraud of the generator, reported 3 days after the transaction
+        # (inside the 7-day delay, so no report may come late); on the device up front, untimed
+        f_idx = np.flatnonzero(d["fraud"])
+        reports = {"due": d["ts"][f_idx] + 3 * day_ns, "ts": T(d["ts"][f_idx], torch.int64),
+                   "terminal": T(d["terminal"][f_idx], torch.int32), "next": 0}
+
+    def report_due(a, ev=None):
+        """the reports due before the batch that starts at row a -> how many"""
+        if a >= len(d["ts"]):
+            return 0
+        lo, hi = reports["next"], int(np.searchsorted(reports["due"], d["ts"][a], side="right"))
+        reports["next"] = hi
+        if ev is not None:
+            ev[0].record()
+        for o in range(lo, hi, cap):
+            sc.report_frauds(reports["ts"][o:min(o + cap, hi)], reports["terminal"][o:min(o + cap, hi)])
+        if ev is not None:
+            ev[1].record()
+        return hi - lo
+
+    def labels(views):  # --fraud-reports: the batch's fraud column is not passed on
+        return views[:4] + [None] if reports is not None else views
     # pinned host copies of the whole input (the "arriving" micro-batches are slices)
     pin = {k: torch.from_numpy(np.ascontiguousarray(d[k])).pin_memory() for k, _ in cols}
     dcols = {k: torch.empty(cap, dtype=t, device=dev) for k, t in cols}
@@ -253,7 +287,7 @@ def main():
         for key, t, w in packed_cols:
             views[key] = dstage[o:o + w * n].view(t)
             o += w * n
-        return [views[key] for key, _ in cols]
+        return labels([views[key] for key, _ in cols])
 
     # one HIP graph per batch size (world 1): the batch's ~10 launches + the probabilities' copy
     # to the host as one graph launch; every size of the streamed day is captured before the
@@ -284,7 +318,7 @@ def main():
             dcols[k][:n].copy_(pin[k][a:b], non_blocking=True)
         if ev is not None:
             ev[0].record()
-        p = sc.score(*(dcols[k][:n] for k, _ in cols))
+        p = sc.score(*labels([dcols[k][:n] for k, _ in cols]))
         if ev is not None:
             ev[1].record()
         out_h[:n].copy_(p, non_blocking=True)
@@ -293,6 +327,8 @@ def main():
 
     t_hist = time.perf_counter()
     for k in range(args.history_days):
+        if reports is not None and day_cuts[k] < day_cuts[k + 1]:
+            report_due(int(day_cuts[k]))
         run(int(day_cuts[k]), int(day_cuts[k + 1]))
     sc.state.check()
     t_hist = time.perf_counter() - t_hist
@@ -309,6 +345,8 @@ def main():
     one = (lambda k, ev=None: run_packed(k, ev)) if packed is not None else \
         (lambda k, ev=None: run(int(bounds[k]), int(bounds[k + 1]), ev))
     for k in range(n_warm):
+        if reports is not None:
+            report_due(int(bounds[k]))
         if wire is not None:
             run_cdc(k)
         else:
@@ -316,7 +354,13 @@ def main():
     if world > 1:
         dist.barrier()
     lat, dev_ms, rows = [], [], 0
+    rep_ms, n_rep = [], 0
     for k in range(n_warm, n_warm + n_timed):
+        if reports is not None:  # before the batch, outside its latency: device time of the report call alone
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            n_rep += report_due(int(bounds[k]), ev)
+            torch.cuda.current_stream().synchronize()
+            rep_ms.append(ev[0].elapsed_time(ev[1]))
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         t0 = time.perf_counter()
         rows += run_cdc(k, ev) if wire is not None else one(k, ev)
@@ -365,6 +409,14 @@ def main():
                        "five pinned columns, one copy each" if packed is None else
                        "one pinned buffer per batch, the five columns back to back (one host-to-device copy)"),
     }
+    if reports is not None:
+        counts = sc.state.label_counts()
+        if counts["late"]:
+            raise SystemExit(f"--fraud-reports: {counts['late']} reports came late (lag 3 days, delay 7)")
+        out.update({"report_p50_ms": round(float(np.percentile(rep_ms, 50)), 3),
+                    "report_unit": "ms (p50 device time of the report_frauds call before each timed batch; "
+                                   "beside device_p50_ms)",
+                    "mean_batch_reports": round(n_rep / max(n_timed, 1), 1), **counts})
     if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)
     if world > 1:

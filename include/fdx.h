@@ -753,6 +753,35 @@ int fdx_stream_status(fdx_stream s, int32_t *flags_h, void *stream);
 /* Non-blocking form: enqueues the copy of the status bits to flags_pinned_h (pinned host
  * memory, valid once the stream reaches this point); does not clear them. */
 int fdx_stream_status_async(fdx_stream s, int32_t *flags_pinned_h, void *stream);
+/* Delayed fraud reports (f-6).  A caller of fdx_stream_update seldom has a row's label when it
+ * scores the row (the CDC topic carries none: it feeds fraud = 0); fraud is confirmed days
+ * later.  fdx_stream_report_frauds takes n <= max_batch reports (ts_d[i] ns, term_d[i]): "the
+ * transaction of terminal term_d[i] at ts_d[i] was fraud", and sets that row's label in the
+ * terminal state as if it had been known all along: the row's ring bit is set and every
+ * boundary count that already passed the row gains 1, so the state equals that of a stream
+ * fed the label with the row.  A report that arrives before the delay boundary passes its row
+ * (no later row of the terminal with ts >= report ts + delay_ns was fed yet) changes no
+ * feature already emitted, and the stream stays bit-identical to the batch path over the true
+ * labels.  Only positive reports exist: a row starts as "not fraud", there is no un-report.
+ * Stream-ordered with fdx_stream_update (same stream, or ordered by the caller: both use the
+ * state's chain arrays); needs terminal state; n == 0 is a no-op; n > max_batch is
+ * FDX_E_INVALID; a terminal id outside [0, n_terminals) raises status bit 4 and is skipped.
+ * Each report ends in exactly one of five outcomes, counted since create / reset:
+ *   on_time    the row was found and the delay boundary had not passed it;
+ *   late       found, but a feature already emitted would have counted the label (the state
+ *              is corrected all the same: later features are those of the true labels);
+ *   duplicate  every live row of that (terminal, ts) already carries the label: no change;
+ *   expired    ts is older than the oldest row the terminal's ring still holds and the ring
+ *              has wrapped: the row left every window (no ring overflow), nothing to correct;
+ *   unmatched  no live row of the terminal has that ts (also: a ts after its last row).
+ * Limit: rows tied on (terminal, ts) are indistinguishable to the terminal features, so a
+ * report marks the first tied row whose label is clear -- a repeated report of one of k tied
+ * rows marks a tied sibling instead of counting as a duplicate (it does once all k are
+ * marked).  A repeated report for an untied row is a duplicate.
+ * fdx_stream_label_counts: counts_h = {on_time, late, duplicate, expired, unmatched};
+ *   synchronises; cumulative since create / reset. */
+int fdx_stream_report_frauds(fdx_stream s, const int64_t *ts_d, const int32_t *term_d, int64_t n, void *stream);
+int fdx_stream_label_counts(fdx_stream s, int64_t counts_h[5], void *stream);
 int fdx_stream_destroy(fdx_stream s);
 
 /* f-4 delay-aware split and Card-Precision@k (shared_functions.py:133-188, :352-411).

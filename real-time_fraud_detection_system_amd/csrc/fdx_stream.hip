@@ -29,6 +29,9 @@
 //                    the head.  Rows of one key in one batch are few (64k rows over 1M
 //                    customers: mostly one), so the chain selection (quadratic in the rows of
 //                    one key in one batch) is short; big bootstrap batches pay it per key.
+// Delayed fraud reports (a row's label is rarely known when the row is scored) = two launches
+// over the reports: k_stream_link (terminal chains only) and k_stream_labels, which sets the
+// row's ring bit and corrects the fraud counts as if the label had been there all along.
 // Latency-bound (a handful of dependent HBM reads per key), no MFMA, no LDS.
 #include <climits>
 
@@ -324,6 +327,82 @@ __global__ void __launch_bounds__(256) k_stream_process(
     }
 }
 
+// Delayed fraud reports (fdx_stream_report_frauds): "the transaction of this terminal at this
+// ts was fraud", arriving after the row was pushed with its bit clear.  Chains built by
+// k_stream_link (customer half null); the thread at a chain's head owns the terminal and
+// visits its reports in (ts, row) order.
+//
+// Invariant: after a report the terminal's record and ring equal those of a stream that had
+// the label on the row from the start.  F[k] counts the fraud bits of ring rows [0, p[k]); a
+// row's bit is read only when p[k] steps over it, so setting the bit of row r and adding 1 to
+// every F[k] with r < p[k] is exactly what those steps would have added.  A report that lands
+// before p[0] (the delay boundary, the first pointer to move) passes the row changes no
+// feature already emitted; one that lands after it is counted late.
+// Only positive reports exist: a row starts as "not fraud" and there is no un-report.
+enum : int { kLabOnTime = 0, kLabLate, kLabDuplicate, kLabExpired, kLabUnmatched, kLabCounters };
+
+template <int W>
+__global__ void __launch_bounds__(256) k_stream_labels(
+    const int64_t *__restrict__ ts, const int32_t *__restrict__ term, int64_t n, int64_t n_term,
+    int32_t *__restrict__ thead, const int32_t *__restrict__ tnext, int64_t *__restrict__ tstate,
+    int64_t *__restrict__ tring, int32_t T, unsigned long long *__restrict__ counts) {
+    constexpr int K = W + 1;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t tk = term[i];
+    if (tk < 0 || tk >= n_term || thead[tk] != (int32_t)i) return;
+    int64_t *rec = tstate + (int64_t)tk * (2 + 2 * K);
+    int64_t *ring = tring + (int64_t)tk * T;
+    const int64_t mask = T - 1;
+    const int64_t nrows = rec[0];
+    int64_t p[K], F[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { p[k] = rec[2 + 2 * k]; F[k] = rec[3 + 2 * k]; }
+    // live ring positions [lo, nrows); non-decreasing in ts unless kStOrder was raised (then a
+    // search may miss its row: unmatched, never out of bounds)
+    int64_t lo = nrows > T ? nrows - T : 0;
+    const int64_t oldest = lo < nrows ? ring[lo & mask] >> 1 : INT64_MAX;
+    const bool evicted = nrows > T;
+    int32_t on_time = 0, late = 0, dup = 0, expired = 0, unmatched = 0;
+    chain_in_order((int32_t)i, tnext, ts, [&](int32_t, int64_t t) {
+        int64_t a = lo, b = nrows;
+        while (a < b) {  // first live row with ts >= t
+            const int64_t mid = (a + b) >> 1;
+            if ((ring[mid & mask] >> 1) < t) a = mid + 1; else b = mid;
+        }
+        lo = a;  // reports come in time order: the next search starts here
+        bool tied = false, found = false;
+        int64_t r = a, e = 0;
+        for (; r < nrows; ++r) {  // among the rows tied on t, the first whose bit is clear
+            e = ring[r & mask];
+            if ((e >> 1) != t) break;
+            tied = true;
+            if (!(e & 1)) { found = true; break; }
+        }
+        if (found) {
+            ring[r & mask] = e | 1;
+#pragma unroll
+            for (int k = 0; k < K; ++k) F[k] += r < p[k] ? 1 : 0;
+        }
+        // expired: the row left the ring; without ring overflow every pointer had passed it, so
+        // no difference F[0] - F[w + 1] a later row sees would change: nothing is written
+        const bool in_time = found && r >= p[0], gone = !tied && evicted && t < oldest;
+        on_time += in_time;
+        late += found && !in_time;
+        dup += tied && !found;
+        expired += gone;
+        unmatched += !tied && !gone;
+    });
+#pragma unroll
+    for (int k = 0; k < K; ++k) rec[3 + 2 * k] = F[k];
+    thead[tk] = -1;
+    if (on_time) atomicAdd(counts + kLabOnTime, (unsigned long long)on_time);
+    if (late) atomicAdd(counts + kLabLate, (unsigned long long)late);
+    if (dup) atomicAdd(counts + kLabDuplicate, (unsigned long long)dup);
+    if (expired) atomicAdd(counts + kLabExpired, (unsigned long long)expired);
+    if (unmatched) atomicAdd(counts + kLabUnmatched, (unsigned long long)unmatched);
+}
+
 bool pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
 
 }  // namespace
@@ -338,6 +417,7 @@ struct fdx_stream_s {
     CEnt *cring_d = nullptr;
     int64_t *cstate_d = nullptr, *tring_d = nullptr, *tstate_d = nullptr;
     int32_t *chead_d = nullptr, *thead_d = nullptr, *cnext_d = nullptr, *tnext_d = nullptr, *status_d = nullptr;
+    unsigned long long *labels_d = nullptr;  // kLabCounters report outcomes since create / reset
     size_t bytes = 0;
 };
 
@@ -357,6 +437,7 @@ extern "C" int fdx_stream_destroy(fdx_stream s) {
     (void)hipFree(s->cnext_d);
     (void)hipFree(s->tnext_d);
     (void)hipFree(s->status_d);
+    (void)hipFree(s->labels_d);
     delete s;
     return FDX_OK;
 }
@@ -373,6 +454,7 @@ extern "C" int fdx_stream_reset(fdx_stream s, void *stream) {
         FDX_HIP(hipMemsetAsync(s->thead_d, 0xFF, (size_t)s->n_term * 4, st));
     }
     FDX_HIP(hipMemsetAsync(s->status_d, 0, 4, st));
+    FDX_HIP(hipMemsetAsync(s->labels_d, 0, kLabCounters * 8, st));
     return FDX_OK;
 }
 
@@ -416,7 +498,8 @@ extern "C" int fdx_stream_create(int64_t n_customers, int64_t n_terminals, int32
         (e = alloc((void **)&s->tstate_d, nt * term_rec_bytes(n_windows))) ||
         (e = alloc((void **)&s->thead_d, nt * 4)) ||
         (e = alloc((void **)&s->cnext_d, (size_t)max_batch * 4)) ||
-        (e = alloc((void **)&s->tnext_d, (size_t)max_batch * 4)) || (e = alloc((void **)&s->status_d, 4))) {
+        (e = alloc((void **)&s->tnext_d, (size_t)max_batch * 4)) || (e = alloc((void **)&s->status_d, 4)) ||
+        (e = alloc((void **)&s->labels_d, kLabCounters * 8))) {
         set_error("hipMalloc of the stream state (%zu bytes so far) failed: %s", s->bytes, hipGetErrorString(e));
         fdx_stream_destroy(s);
         return FDX_E_HIP;
@@ -478,6 +561,49 @@ extern "C" int fdx_stream_update(fdx_stream s, const int64_t *ts_d, const int32_
         FDX_STREAM_PROCESS(8)
     }
     FDX_LAUNCHED("k_stream_process");
+    return FDX_OK;
+}
+
+#define FDX_STREAM_LABELS(WW)                                                                                    \
+    case WW:                                                                                                     \
+        hipLaunchKernelGGL(k_stream_labels<WW>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, ts_d, term_d, \
+                           n, s->n_term, s->thead_d, s->tnext_d, s->tstate_d, s->tring_d, s->T, s->labels_d);     \
+        break;
+
+extern "C" int fdx_stream_report_frauds(fdx_stream s, const int64_t *ts_d, const int32_t *term_d, int64_t n,
+                                        void *stream) {
+    FDX_REQUIRE(s, "null stream state");
+    FDX_REQUIRE(n >= 0 && n <= s->max_batch, "batch of %lld reports exceeds max_batch %lld", (long long)n,
+                (long long)s->max_batch);
+    if (n == 0) return FDX_OK;
+    FDX_REQUIRE(ts_d && term_d, "null ts or terminal");
+    FDX_REQUIRE(s->n_term, "fraud reports need terminal state");
+    hipStream_t st = as_stream(stream);
+    // terminal chains only (customer half null): flags an id out of range, writes no X
+    hipLaunchKernelGGL(k_stream_link, dim3(stream_grid(n, 256)), dim3(256), 0, st, ts_d, (const int32_t *)nullptr,
+                       (const double *)nullptr, term_d, n, s->n_cust, s->n_term, s->chead_d, s->cnext_d, s->thead_d,
+                       s->tnext_d, s->mode, (double *)nullptr, (int64_t)0, s->status_d);
+    FDX_LAUNCHED("k_stream_link");
+    switch (s->W) {
+        FDX_STREAM_LABELS(1)
+        FDX_STREAM_LABELS(2)
+        FDX_STREAM_LABELS(3)
+        FDX_STREAM_LABELS(4)
+        FDX_STREAM_LABELS(5)
+        FDX_STREAM_LABELS(6)
+        FDX_STREAM_LABELS(7)
+        FDX_STREAM_LABELS(8)
+    }
+    FDX_LAUNCHED("k_stream_labels");
+    return FDX_OK;
+}
+
+extern "C" int fdx_stream_label_counts(fdx_stream s, int64_t counts_h[5], void *stream) {
+    FDX_REQUIRE(s && counts_h, "null pointer");
+    static_assert(kLabCounters == 5, "fdx.h documents five counters");
+    hipStream_t st = as_stream(stream);
+    FDX_HIP(hipMemcpyAsync(counts_h, s->labels_d, kLabCounters * 8, hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
     return FDX_OK;
 }
 

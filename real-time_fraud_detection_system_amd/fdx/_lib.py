@@ -108,6 +108,8 @@ SIGNATURES = {
     "fdx_stream_update": (ctypes.c_int, [P, P, P, P, P, P, c_i64, P, c_i64, c_i32, P, P, P, P]),
     "fdx_stream_status": (ctypes.c_int, [P, P, P]),
     "fdx_stream_status_async": (ctypes.c_int, [P, P, P]),
+    "fdx_stream_report_frauds": (ctypes.c_int, [P, P, P, c_i64, P]),
+    "fdx_stream_label_counts": (ctypes.c_int, [P, P, P]),
     "fdx_stream_destroy": (ctypes.c_int, [P]),
     "fdx_train_test_split": (ctypes.c_int, [P, P, P, P, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, P, P, P,
                                             c_sz, P, P]),

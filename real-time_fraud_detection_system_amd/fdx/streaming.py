@@ -10,7 +10,16 @@ the same 15 features, bit for bit, as the batch path over the whole history
 (get_customer_spending_behaviour_features feature_transformation.ipynb:601-628,
 get_count_risk_rolling_window :1495-1522, tests/test_gpu_stream.py).
 
-  StreamState          device state + fdx_stream_update (features of a batch)
+That identity is over the TX_FRAUD labels, and no live caller has a row's label when it
+scores the row: the reference's Postgres table and Debezium topic carry no TX_FRAUD, fraud
+is confirmed days later (which is why the terminal windows are delayed, :1495-1522).  Rows
+are therefore fed unlabelled (fraud=None; score_cdc feeds zeros) and the labels arrive through
+report_frauds, which sets them in the terminal state as if known all along; reports that
+arrive within the delay keep the stream bit-identical to the batch path over the true labels
+(tests/test_gpu_stream_labels.py).
+
+  StreamState          device state + fdx_stream_update (features of a batch) +
+                       fdx_stream_report_frauds (delayed labels)
   StreamScorer         StreamState + the forest (scale + predict_proba) per batch
   ShardedStreamScorer  one process per GPU: customers sharded by id range, terminals owned
                        by id % world, one RCCL all-to-all there and back per batch (the
@@ -28,6 +37,7 @@ from ._lib import FdxError, FdxUnsupported, check
 
 _STATUS = {1: "customer ring overflow (raise customer_ring)", 2: "terminal ring overflow (raise terminal_ring)",
            4: "customer or terminal id outside the state's capacity", 8: "a key's rows went back in time"}
+LABEL_OUTCOMES = ("on_time", "late", "duplicate", "expired", "unmatched")  # fdx_stream_label_counts
 
 
 class StreamState:
@@ -98,6 +108,29 @@ class StreamState:
                                             ops._s(stream)), "fdx_stream_update")
         return X
 
+    def report_frauds(self, ts, terminal, stream=None):
+        """Delayed fraud reports (device tensors; int64 ns, int32 ids): the transaction of
+        terminal[i] at ts[i] was fraud.  Sets the row's label in the terminal state as if it had
+        been known all along (include/fdx.h: the five outcomes, the limit on tied rows); a
+        report that arrives within the delay changes no feature already emitted.  Positive
+        reports only.  Stream-ordered with update(); state addresses do not move, so a captured
+        score_graph stays valid."""
+        ops._dev(ts, torch.int64, "ts")
+        ops._dev(terminal, torch.int32, "terminal")
+        n = ts.numel()
+        if terminal.numel() != n:
+            raise FdxError(f"terminal has {terminal.numel()} rows, ts has {n}")
+        if n > self.max_batch:
+            raise FdxError(f"batch of {n} reports > max_batch {self.max_batch}")
+        check(_lib.load().fdx_stream_report_frauds(self._h, ops._ptr(ts), ops._ptr(terminal), n, ops._s(stream)),
+              "fdx_stream_report_frauds")
+
+    def label_counts(self, stream=None) -> dict:
+        """Synchronise; -> the outcomes of the reports since create / reset."""
+        c = (ctypes.c_int64 * len(LABEL_OUTCOMES))()
+        check(_lib.load().fdx_stream_label_counts(self._h, c, ops._s(stream)), "fdx_stream_label_counts")
+        return dict(zip(LABEL_OUTCOMES, (int(v) for v in c)))
+
     def check(self, stream=None):
         """Synchronise and raise if a kernel reported a problem since the last check."""
         f = ctypes.c_int32()
@@ -153,13 +186,31 @@ class StreamScorer:
         self.ws = ops.workspace(forest.workspace_size_max(max_batch), dev)
         self.proba = torch.empty(max_batch, dtype=torch.float64, device=dev)
 
-    def score(self, ts, customer, amount, terminal, fraud):
+    def _no_labels(self, n):
+        """fraud = None: the batch's labels are not known yet (report_frauds brings them).  One
+        zero buffer for every batch size, so score_graph's key (its address) stays stable."""
+        z = getattr(self, "_zero_fraud", None)
+        if z is None:
+            z = self._zero_fraud = torch.zeros(self.state.max_batch, dtype=torch.uint8, device=self.state.device)
+        return z[:n]
+
+    def report_frauds(self, ts, terminal):
+        """StreamState.report_frauds on the current stream, with score()'s status polling (a
+        terminal id out of range raises at the next call or finish())."""
+        self.state.poll()
+        self.state.report_frauds(ts, terminal)
+        self.state.watch()
+
+    def score(self, ts, customer, amount, terminal, fraud=None):
         """-> predict_proba[:, 1] of the batch (device view, valid until the next call).
+        fraud None: no labels yet (zeros; report_frauds brings them later).
         Ring overflows, ids out of range and rows that go back in time are flagged by the
         kernels; every batch enqueues a non-blocking copy of those bits and the next score()
         (or finish()) raises FdxUnsupported for the batch that set them."""
         self.state.poll()
         n = ts.numel()
+        if fraud is None:
+            fraud = self._no_labels(n)
         if not self.fused:
             X = self.state.update(ts, customer, amount, terminal, fraud, X=self.X[:n])
             out = self.forest.predict(X, ws=self.ws, out=self.proba[:n])
@@ -180,7 +231,7 @@ class StreamScorer:
         """Wait for the last batch's status bits and raise if it reported a problem."""
         self.state.poll(block=True)
 
-    def score_graph(self, ts, customer, amount, terminal, fraud, out_host=None, replay: bool = True):
+    def score_graph(self, ts, customer, amount, terminal, fraud=None, out_host=None, replay: bool = True):
         """score() replayed from a HIP graph: the batch's kernels (state update, row assembly,
         forest walk, tree sums), its status-word copy and -- with out_host (pinned, float64,
         >= n) -- the probabilities' copy to the host are captured once per (batch size, buffer
@@ -194,6 +245,8 @@ class StreamScorer:
         if replay:
             self.state.poll()
         n = ts.numel()
+        if fraud is None:
+            fraud = self._no_labels(n)
         key = (n, self.forest.epoch) + tuple(t.data_ptr() for t in (ts, customer, amount, terminal, fraud)) + \
             ((out_host.data_ptr(),) if out_host is not None else ())
         graphs = self.__dict__.setdefault("_graphs", {})
@@ -237,7 +290,8 @@ class StreamScorer:
         fdx_cdc_compact (kept records, batch order) -> score().  Inputs are device tensors:
         tx_id / customer_id / terminal_id / tx_datetime_us / kafka_ts int64 [n], amount_bytes
         uint8 (the records' bytes back to back), amount_offsets int64 [n + 1], fraud uint8 [n]
-        or None (the CDC topic carries no label: zeros).  One host read per batch (the kept
+        or None (the CDC topic carries no label: zeros; the TERMINAL_ID_RISK features then see
+        only what report_frauds delivered).  One host read per batch (the kept
         count).  -> (proba [m] device view, rows int32 [m] = batch position of each kept record)."""
         L = _lib.load()
         n = tx_id.numel()
