@@ -19,7 +19,12 @@ is the max over ranks.  Rank 0 prints one JSON line.
 fraud reports before each batch (StreamScorer.report_frauds); the line gains the report call's
 device time and the five report outcomes.
 
-usage: python bench_stream.py [--gpus N] [--batches K] [--warmup W] [--fraud-reports]
+--snapshot: after the streamed day, the state's snapshot (StreamState.snapshot's C call) and its
+restore into a second state of the same geometry are timed with HIP events, alternated with a
+device-to-device copy of a buffer of the snapshot's size (the yardstick); the line gains a
+"snapshot" object.  The default line is unchanged.
+
+usage: python bench_stream.py [--gpus N] [--batches K] [--warmup W] [--fraud-reports] [--snapshot]
 """
 import argparse
 import json
@@ -106,7 +111,82 @@ def parse(argv=None):
                     help="rows are fed unlabelled (fraud=None); before each batch the fraud reports due by then "
                          "(the generator's labels, 3 days after the transaction) go in through "
                          "StreamScorer.report_frauds, timed on their own (world 1, not with --cdc)")
+    ap.add_argument("--snapshot", action="store_true",
+                    help="after the streamed day: time the state's snapshot and its restore into a second state "
+                         "against a device-to-device copy of the same size (world 1)")
+    ap.add_argument("--snapshot-repeats", type=int, default=10)
     return ap.parse_args(argv)
+
+
+def measure_snapshot(state, repeats=10):
+    """Time fdx_stream_snapshot and fdx_stream_restore (into a second state of the same geometry)
+    of `state` with HIP events, each alternated with a device-to-device copy of a buffer of the
+    snapshot's size; one warm-up round, then `repeats`.  The calls synchronise inside (status and
+    counts come to the host), so the event times are those of the whole call.  -> dict."""
+    import numpy as np
+    import torch
+
+    from fdx import _lib, ops
+    from fdx.streaming import StreamState, snapshot_info
+
+    L = _lib.load()
+    snap = state.snapshot()
+    f = snapshot_info(snap)
+    nbytes = snap.numel()
+    second = StreamState(state.n_customers, state.n_terminals, state.windows_days, state.delay_days,
+                         state.customer_ring, state.terminal_ring, 1, state.flags_mode)
+    second.restore(snap, counters=False)
+    if not torch.equal(second.snapshot(), snap):
+        raise SystemExit("--snapshot: the restored state's snapshot differs from the source's")
+    copy_dst = torch.empty_like(snap)
+    ws = state._snap_ws()
+    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+    ms = {"snapshot": [], "restore": [], "copy": []}
+    for i in range(repeats + 1):
+        pairs = {k: (ev(), ev()) for k in ("snapshot", "copy_a", "restore", "copy_b")}
+        pairs["snapshot"][0].record()
+        _lib.check(L.fdx_stream_snapshot(state._h, None, None, ops._ptr(snap), nbytes, None, ops._ptr(ws), ws.numel(),
+                                         ops._s()), "fdx_stream_snapshot")
+        pairs["snapshot"][1].record()
+        pairs["copy_a"][0].record()
+        copy_dst.copy_(snap)
+        pairs["copy_a"][1].record()
+        pairs["restore"][0].record()
+        second.restore(snap, counters=False)
+        pairs["restore"][1].record()
+        pairs["copy_b"][0].record()
+        copy_dst.copy_(snap)
+        pairs["copy_b"][1].record()
+        torch.cuda.synchronize()
+        if i:  # round 0 warms up
+            ms["snapshot"].append(pairs["snapshot"][0].elapsed_time(pairs["snapshot"][1]))
+            ms["restore"].append(pairs["restore"][0].elapsed_time(pairs["restore"][1]))
+            ms["copy"] += [pairs[k][0].elapsed_time(pairs[k][1]) for k in ("copy_a", "copy_b")]
+    W = f["n_windows"]
+    rec = f["customer_keys"] * (2 + 6 * W) * 8 + f["terminal_keys"] * (4 + 2 * W) * 8
+    ent = f["customer_entries"] * 16 + f["terminal_entries"] * 8
+    off = (f["customer_keys"] + f["terminal_keys"] + 2) * 8
+    keys4 = (f["customer_keys"] + f["terminal_keys"] + 2) * 4
+    # from the header's counts.  snapshot: the count pass reads the records and writes + scans the
+    # u32 counts, the pack reads records + counts + entries and writes records + offsets + entries;
+    # restore: the validation reads records + offsets, the unpack reads all and writes records + entries
+    moved = {"snapshot": rec + 3 * keys4 + (rec + keys4 + ent) + (rec + off + ent),
+             "restore": (rec + off) + (rec + off + ent) + (rec + ent), "copy": 2 * nbytes}
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    return {"snapshot_bytes": nbytes, "customer_max_live": f["customer_max_live"],
+            "terminal_max_live": f["terminal_max_live"], "customer_entries": f["customer_entries"],
+            "terminal_entries": f["terminal_entries"], "repeats": repeats,
+            "snapshot_ms": round(med["snapshot"], 3), "restore_ms": round(med["restore"], 3),
+            "copy_ms": round(med["copy"], 3),
+            "snapshot_ms_all": [round(v, 3) for v in ms["snapshot"]],
+            "restore_ms_all": [round(v, 3) for v in ms["restore"]],
+            "copy_ms_all": [round(v, 3) for v in ms["copy"]],
+            "bytes_moved": moved,
+            "gb_per_s": {k: round(moved[k] / (med[k] * 1e-3) / 1e9, 1) for k in moved},
+            "snapshot_over_copy": round(med["snapshot"] / med["copy"], 2),
+            "restore_over_copy": round(med["restore"] / med["copy"], 2),
+            "unit": "ms (median HIP-event time of the whole call, host synchronisations inside included); "
+                    "copy = device-to-device copy of snapshot_bytes, alternated with the calls"}
 
 
 def rank_shard(args, world: int, rank: int):
@@ -417,6 +497,10 @@ def main():
                     "report_unit": "ms (p50 device time of the report_frauds call before each timed batch; "
                                    "beside device_p50_ms)",
                     "mean_batch_reports": round(n_rep / max(n_timed, 1), 1), **counts})
+    if args.snapshot:
+        if world > 1:
+            raise SystemExit("--snapshot runs at world 1")
+        out["snapshot"] = measure_snapshot(sc.state, args.snapshot_repeats)
     if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)
     if world > 1:

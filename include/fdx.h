@@ -783,6 +783,80 @@ int fdx_stream_status_async(fdx_stream s, int32_t *flags_pinned_h, void *stream)
 int fdx_stream_report_frauds(fdx_stream s, const int64_t *ts_d, const int32_t *term_d, int64_t n, void *stream);
 int fdx_stream_label_counts(fdx_stream s, int64_t counts_h[5], void *stream);
 int fdx_stream_destroy(fdx_stream s);
+/* State snapshot and restore (f-7).  A snapshot is one flat buffer in caller-owned device memory
+ * (16-byte aligned), built from little-endian 8-byte words; it can be copied byte for byte to
+ * the host or a file.  It restores into a state of any ring size and key capacity that fits.
+ *   Header, FDX_SNAPSHOT_HEADER_BYTES = 64 words:
+ *     0 magic (the bytes "FDXSNAP1")   1 format version (1)   2 total bytes   3 n_windows
+ *     4..11 window_ns[8] (unused: 0)   12 delay_ns   13 flags_mode
+ *     14 customer_ring, 15 terminal_ring of the source state
+ *     16 customer keys   17 customer entries   18 customer max_live (the largest live row count
+ *     of a carried key)   19..21 the same for terminals
+ *     22..26 the label counters {on_time, late, duplicate, expired, unmatched}
+ *     27..32 byte offsets of the six sections, in the order below   33..63 zero
+ *   Sections, back to back after the header, each padded with zeros to a multiple of 16 bytes:
+ *     customer records   keys x [n, last_ts, (tail, sum, c_add, c_rem, prev, nobs | nsame << 32) x W]
+ *     customer offsets   int64[keys + 1]: key j's entries are [offsets[j], offsets[j + 1])
+ *     customer entries   {int64 ts, double amount}, 16 bytes, oldest first
+ *     terminal records   keys x [n, last_ts, (p_k, F_k) x (W + 1)]    k = 0: delay, k = w + 1: delay + w
+ *     terminal offsets   int64[keys + 1]
+ *     terminal entries   ts << 1 | fraud, 8 bytes, oldest first
+ *   Live range: of a key's n rows only ring positions [lo, n) are carried, lo = min_w tail[w]
+ *   (customer) resp. min_k p[k] (terminal).  Rows before lo have left every window and cannot
+ *   re-enter one, because a key's time does not go back.  n, tail[w] and p[k] are stored minus
+ *   lo (the first carried row is position 0); every other word keeps its value (last_ts, the
+ *   Kahan words, nobs | nsame << 32, F[k]: only differences of F are ever used).  A key with
+ *   n == 0 carries nothing; a key with n >= 1 carries at least one row.
+ *   Canonical: the same state and selection give the same bytes whatever the source's ring
+ *   sizes or the thread scheduling -- except header words 14 and 15, which name the source's
+ *   ring sizes (the defaults of a state built from the snapshot).
+ *   Consequence: a fraud report for a row the snapshot dropped finds no row in the restored
+ *   state and counts as unmatched (it would have counted as late; such a row cannot affect any
+ *   feature).  Reports for carried rows behave exactly as before.
+ * A key selection (first, count, step) picks keys first + j * step, j in [0, count); NULL =
+ * every key (count 0 = none of that half).  Customer shards use step 1, terminal ownership
+ * t % world uses first = rank, step = world.
+ * fdx_stream_snapshot_size runs the count pass and returns the byte count (synchronises: a cold
+ *   path).  fdx_stream_snapshot recounts and writes; FDX_E_INVALID when snap_bytes is too small;
+ *   *written_h (optional) = the byte count.  Both are stream-ordered after earlier updates on
+ *   `stream`, and both read the status word first: a set bit is FDX_E_UNSUPPORTED and stays set
+ *   (a flagged state is not worth saving).  A half with 2^32 or more entries is FDX_E_INVALID.
+ *   Workspace: fdx_stream_snapshot_workspace_size(s) bytes (also enough for fdx_stream_restore).
+ * fdx_stream_snapshot_info: host only.  header_h = at least the header's bytes, bytes = the byte
+ *   count of the buffer they head.  Checks magic, version, n_windows, the counts' ranges, that
+ *   the section offsets are those of the layout above and end at the total, total <= bytes.
+ * fdx_stream_restore: snapshot key j lands on state key first + j * step (identity: 0, 1).
+ *   FDX_E_INVALID with a message and NOTHING written when: fdx_stream_snapshot_info fails; the
+ *   windows or the delay differ from the state's; a destination key is beyond the capacity; a
+ *   half is carried that the state does not have; the offsets or pointers are malformed; a
+ *   key's live count exceeds the state's ring (the message names the first such key and its
+ *   count).  The last two come from a device pass that completes before the write pass starts
+ *   (the call synchronises).  Written keys are overwritten, all others untouched: restores into
+ *   disjoint key sets merge.  FDX_RESTORE_COUNTERS adds the snapshot's label counters to the
+ *   state's.  State addresses do not move: a captured graph of updates stays valid. */
+#define FDX_SNAPSHOT_HEADER_BYTES 512
+#define FDX_RESTORE_COUNTERS 1
+typedef struct {
+    int64_t first, count, step;
+} fdx_key_selection;
+typedef struct {
+    int64_t version, total_bytes, n_windows, window_ns[FDX_MAX_WINDOWS], delay_ns, flags_mode;
+    int64_t customer_ring, terminal_ring;
+    int64_t customer_keys, customer_entries, customer_max_live;
+    int64_t terminal_keys, terminal_entries, terminal_max_live;
+    int64_t label_counts[5];
+    int64_t section_offset[6];
+} fdx_snapshot_info;
+size_t fdx_stream_snapshot_workspace_size(fdx_stream s);
+int fdx_stream_snapshot_size(fdx_stream s, const fdx_key_selection *customers, const fdx_key_selection *terminals,
+                             size_t *bytes_h, void *workspace_d, size_t workspace_bytes, void *stream);
+int fdx_stream_snapshot(fdx_stream s, const fdx_key_selection *customers, const fdx_key_selection *terminals,
+                        void *snap_d, size_t snap_bytes, size_t *written_h, void *workspace_d,
+                        size_t workspace_bytes, void *stream);
+int fdx_stream_snapshot_info(const void *header_h, size_t bytes, fdx_snapshot_info *out);
+int fdx_stream_restore(fdx_stream s, const void *snap_d, size_t snap_bytes, int64_t customer_first,
+                       int64_t customer_step, int64_t terminal_first, int64_t terminal_step, int32_t flags,
+                       void *workspace_d, size_t workspace_bytes, void *stream);
 
 /* f-4 delay-aware split and Card-Precision@k (shared_functions.py:133-188, :352-411).
  * fdx_train_test_split: train_d[i] = t_lo <= ts_d[i] < t_hi; test_d[i] = the row is on test

@@ -34,6 +34,8 @@
 // row's ring bit and corrects the fraud counts as if the label had been there all along.
 // Latency-bound (a handful of dependent HBM reads per key), no MFMA, no LDS.
 #include <climits>
+#include <cstdlib>
+#include <cstring>
 
 #include "fdx_internal.h"
 
@@ -622,3 +624,513 @@ extern "C" int fdx_stream_status_async(fdx_stream s, int32_t *flags_pinned_h, vo
     return FDX_OK;
 }
 
+
+// ---------------------------------------------------------------- snapshot / restore (f-7)
+// The live state as one flat, self-describing buffer of little-endian 8-byte words (format:
+// include/fdx.h).  Per key only the LIVE rows travel: ring positions [min pointer, n), where
+// the pointers are the customer's tail[w] resp. the terminal's p[k].  A row before every
+// pointer has left every window and cannot re-enter one (a key's time does not go back), so
+// the update kernels never read it again; n and the pointers are rebased to the first carried
+// row, every other word (last_ts, the Kahan words, nobs | nsame << 32, F[k] -- only differences
+// of F are used) keeps its value.  The bytes do not depend on the source's ring size, so a
+// snapshot restores into any ring that holds the longest live run and any key capacity.
+//
+//   k_snap_count     8 lanes per selected key: live count -> u32 array (then the exclusive
+//                    scan of fdx_rekey.hip gives the entry offsets), max and 64-bit sum
+//   k_snap_pack      a group of 2^gshift lanes per key: record words (rebased) and the live
+//                    rows, consecutive lanes on consecutive ring entries -- a key's rows are
+//                    one or two contiguous runs of its ring, and rings sit ring * 16 B apart,
+//                    so one thread per key would touch 64 different rows per wave
+//   k_snap_header    the 64 header words, the closing offset of both halves, zero padding
+//   k_snap_validate  restore, pass 1: one thread per key checks offsets and pointers and that
+//                    the live count fits the destination ring; reads only inside the sections
+//                    whose sizes the host checked against the byte count
+//   k_snap_unpack    restore, pass 2 (only after pass 1 came back clean): group per key
+// Bandwidth-bound copies through vector loads / stores; no LDS.
+namespace fdx {
+namespace {
+
+constexpr uint64_t kSnapMagic = 0x3150414E53584446ull;  // the bytes "FDXSNAP1"
+constexpr int kSnapVersion = 1;
+enum : int {  // header word indices (include/fdx.h)
+    kHMagic = 0, kHVersion, kHBytes, kHWindows, kHWin0,
+    kHDelay = kHWin0 + kMaxW, kHMode, kHCRing, kHTRing,
+    kHCKeys, kHCEntries, kHCMaxLive, kHTKeys, kHTEntries, kHTMaxLive,
+    kHLabels, kHOff = kHLabels + kLabCounters, kHUsed = kHOff + 6, kHWords = 64
+};
+static_assert(kHWords * 8 == FDX_SNAPSHOT_HEADER_BYTES && kHUsed <= kHWords && kHDelay == 12 && kHOff == 27,
+              "fdx.h documents the header words");
+
+struct SnapHeader { int64_t w[kHWords]; };
+
+// device-side results of the count / validate passes (zeroed, resp. preset, before each pass)
+struct SnapRes {
+    unsigned long long total[2], max_live[2];  // [0] customers, [1] terminals
+    unsigned long long small[2];               // validate: min over keys of (key << 32 | live) that do not fit
+    uint32_t bad, pad;                         // count: bit h = half h inconsistent; validate: malformed
+};
+
+struct Sel { int64_t first, count, step; };
+
+struct Half {  // what the generic kernels need to know about one half
+    int64_t *state;
+    void *ring;
+    int64_t n_keys;
+    int32_t R, pstride, np, ring_len;  // record words; pointers at words 2 + k * pstride, k < np
+};
+
+uint64_t round16(uint64_t b) { return (b + 15) & ~(uint64_t)15; }
+
+// Section offsets of the canonical layout; counts already range-checked (keys <= INT32_MAX,
+// entries < 2^32), so nothing overflows 64 bits.
+void snap_layout(int W, uint64_t ck, uint64_t ce, uint64_t tk, uint64_t te, uint64_t off[6], uint64_t *total) {
+    uint64_t o = (uint64_t)kHWords * 8;
+    off[0] = o; o += ck * cust_rec_bytes(W);
+    off[1] = o; o += round16((ck + 1) * 8);
+    off[2] = o; o += ce * sizeof(CEnt);
+    off[3] = o; o += tk * term_rec_bytes(W);
+    off[4] = o; o += round16((tk + 1) * 8);
+    off[5] = o; o += round16(te * 8);
+    *total = o;
+}
+
+// n and lo = min(n, pointers) of one record, read by a group of G = 2^k lanes with consecutive
+// lanes on consecutive words (one thread per record would put 64 lanes on 64 records 80-160 B
+// apart and wait for its pointer loads one after the other: 570 us per launch at config 5).
+// Every lane of the group gets both.  Pointers sit at words 2 + k * pstride, all of them below R.
+__device__ __forceinline__ bool snap_rebased(int32_t i, int32_t pstride) {
+    return i == 0 || (i >= 2 && (i - 2) % pstride == 0);
+}
+__device__ __forceinline__ void group_live_range(const int64_t *__restrict__ rec, int32_t R, int32_t pstride,
+                                                 int32_t lane, int32_t G, int64_t &n, int64_t &lo) {
+    int64_t m = INT64_MAX, n0 = 0;
+    for (int32_t i = lane; i < R; i += G) {
+        const int64_t v = rec[i];
+        if (i == 0) n0 = v;
+        if (snap_rebased(i, pstride)) m = imin64(m, v);
+    }
+    for (int32_t d = G >> 1; d >= 1; d >>= 1) m = imin64(m, __shfl_xor(m, d, G));
+    n = __shfl(n0, 0, G);
+    lo = m;
+}
+
+constexpr int kCountShift = 3;  // k_snap_count: 8 lanes per key
+
+__global__ void __launch_bounds__(256) k_snap_count(const int64_t *__restrict__ state, int32_t R, int32_t pstride,
+                                                    int64_t ring, Sel sel, uint32_t *__restrict__ cnt,
+                                                    SnapRes *__restrict__ res, int32_t half) {
+    constexpr int32_t G = 1 << kCountShift;
+    const int32_t lane = (int32_t)threadIdx.x & (G - 1);
+    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> kCountShift;
+    // Grid-stride over the keys, so that a wave ends in ONE set of atomics on the result words:
+    // with a wave per 64 keys (47k waves at config 5) the launch took 570 us, with a wave per 8
+    // keys 4.4 ms -- the same-address atomics, not the loads, were its time.
+    unsigned long long sum = 0, mx = 0;
+    uint32_t bad = 0;
+    for (int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> kCountShift; j <= sel.count; j += groups) {
+        unsigned long long live = 0;
+        if (j < sel.count) {  // the whole group or none of it
+            int64_t n, lo;
+            group_live_range(state + (sel.first + j * sel.step) * R, R, pstride, lane, G, n, lo);
+            int64_t l = n - lo;
+            // a consistent state has 0 <= lo, one live row when n >= 1, and the live rows in the ring
+            if (lo < 0 || l > ring || (n > 0 && l < 1)) {
+                bad = 1u << half;
+                l = 0;
+            }
+            live = (unsigned long long)l;
+        }
+        if (lane == 0) {  // j == count: cnt[count] = 0 closes the scan
+            cnt[j] = (uint32_t)live;
+            sum += live;
+            mx = live > mx ? live : mx;
+        }
+    }
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) {
+        sum += __shfl_xor(sum, d, kWave);
+        const unsigned long long o = __shfl_xor(mx, d, kWave);
+        mx = o > mx ? o : mx;
+        bad |= __shfl_xor(bad, d, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        if (sum) atomicAdd(&res->total[half], sum);
+        if (mx) atomicMax(&res->max_live[half], mx);
+        if (bad) atomicOr(&res->bad, bad);
+    }
+}
+
+template <class E>
+__global__ void __launch_bounds__(256) k_snap_pack(const int64_t *__restrict__ state, const E *__restrict__ rings,
+                                                   int32_t R, int32_t pstride, int64_t ring, Sel sel,
+                                                   const uint32_t *__restrict__ off, int64_t *__restrict__ out_rec,
+                                                   int64_t *__restrict__ out_off, E *__restrict__ out_ent,
+                                                   int32_t gshift) {
+    const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> gshift;
+    if (g >= sel.count) return;  // the whole group or none of it
+    const int32_t G = 1 << gshift, lane = (int32_t)threadIdx.x & (G - 1);
+    const int64_t key = sel.first + g * sel.step;
+    const int64_t *rec = state + key * R;
+    // the entry range comes from the count pass, so the writes stay inside what the host sized
+    const int64_t o = off[g], live = (int64_t)off[g + 1] - o;
+    int64_t n, lo;
+    group_live_range(rec, R, pstride, lane, G, n, lo);
+    for (int32_t i = lane; i < R; i += G)  // (the words again, from cache) n and the pointers: rebased
+        out_rec[g * R + i] = rec[i] - (snap_rebased(i, pstride) ? lo : 0);
+    if (lane == 0) out_off[g] = o;
+    const E *rg = rings + key * ring;
+    const int64_t mask = ring - 1;
+#pragma unroll 4
+    for (int64_t i = lane; i < live; i += G) out_ent[o + i] = rg[(lo + i) & mask];
+}
+
+struct SnapTail {  // words k_snap_header writes besides the header: closing offsets, zero padding
+    int64_t word[5], value[5];
+    int32_t n;
+};
+
+__global__ void __launch_bounds__(64) k_snap_header(int64_t *__restrict__ dst, SnapHeader h, SnapTail t,
+                                                   const unsigned long long *__restrict__ labels) {
+    const int i = threadIdx.x;
+    int64_t v = h.w[i];
+    if (i >= kHLabels && i < kHLabels + kLabCounters) v = (int64_t)labels[i - kHLabels];
+    dst[i] = v;
+    if (i < t.n) dst[t.word[i]] = t.value[i];
+}
+
+__global__ void __launch_bounds__(256) k_snap_validate(const int64_t *__restrict__ rec_d, const int64_t *__restrict__ off,
+                                                       int32_t R, int32_t pstride, int32_t np, int64_t keys,
+                                                       int64_t entries, int64_t ring, SnapRes *__restrict__ res,
+                                                       int32_t half) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= keys) return;
+    const int64_t o0 = off[j], o1 = off[j + 1];
+    const int64_t *rec = rec_d + j * R;
+    const int64_t n = rec[0];
+    bool bad = o0 < 0 || o1 < o0 || o1 > entries || (j == 0 && o0 != 0) || (j == keys - 1 && o1 != entries) ||
+               n != o1 - o0;
+    for (int k = 0; k < np; ++k) {
+        const int64_t p = rec[2 + k * pstride];
+        bad |= p < 0 || p > n;
+    }
+    if (bad) {
+        atomicOr(&res->bad, 1u << half);
+    } else if (n > ring) {
+        const unsigned long long c = n > 0xFFFFFFFFll ? 0xFFFFFFFFull : (unsigned long long)n;
+        atomicMin(&res->small[half], ((unsigned long long)j << 32) | c);
+    }
+}
+
+template <class E>
+__global__ void __launch_bounds__(256) k_snap_unpack(const int64_t *__restrict__ rec_d, const int64_t *__restrict__ off,
+                                                     const E *__restrict__ ent, int32_t R, int64_t keys, int64_t first,
+                                                     int64_t step, int64_t ring, int64_t *__restrict__ state,
+                                                     E *__restrict__ rings, int32_t gshift) {
+    const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> gshift;
+    if (g >= keys) return;
+    const int32_t G = 1 << gshift, lane = (int32_t)threadIdx.x & (G - 1);
+    const int64_t key = first + g * step;
+    for (int32_t i = lane; i < R; i += G) state[key * R + i] = rec_d[g * R + i];
+    // validated: 0 <= off[g] <= off[g + 1] <= entries and off[g + 1] - off[g] <= ring
+    const int64_t o = off[g], live = off[g + 1] - o;
+    E *rg = rings + key * ring;
+#pragma unroll 4
+    for (int64_t i = lane; i < live; i += G) rg[i] = ent[o + i];
+}
+
+__global__ void __launch_bounds__(64) k_snap_add_labels(unsigned long long *__restrict__ labels, SnapHeader h) {
+    if (threadIdx.x < kLabCounters) labels[threadIdx.x] += (unsigned long long)h.w[kHLabels + threadIdx.x];
+}
+
+size_t al256(size_t b) { return round_up(b, 256); }
+
+// Lanes per key: 16, the fastest of 4 .. 64 at config 5 (58 live rows per customer on average,
+// 160 at most: profiles/stream_snapshot.json; a group covering the longest run, 64, was the
+// slowest); narrower, down to 4, when no key has that many live rows.  FDX_SNAP_GROUP overrides
+// it for that measurement.
+int32_t snap_gshift(int64_t max_live) {
+    if (const char *e = getenv("FDX_SNAP_GROUP")) {
+        const int g = atoi(e);
+        for (int sh = 0; sh <= 6; ++sh)
+            if (g == (1 << sh)) return sh;
+    }
+    int32_t sh = 2;
+    while (sh < 4 && (1ll << sh) < max_live) ++sh;
+    return sh;
+}
+
+unsigned group_grid(int64_t keys, int32_t gshift) { return (unsigned)ceil_div(keys << gshift, 256); }
+
+Half cust_half(fdx_stream s) {
+    return Half{s->cstate_d, s->cring_d, s->n_cust, 2 + 6 * s->W, 6, s->W, s->C};
+}
+Half term_half(fdx_stream s) {
+    return Half{s->tstate_d, s->tring_d, s->n_term, 4 + 2 * s->W, 2, s->W + 1, s->T};
+}
+
+struct SnapWs {
+    SnapRes *res;
+    uint32_t *cnt[2];
+    void *scan;
+};
+
+SnapWs snap_ws(fdx_stream s, void *ws) {
+    char *p = reinterpret_cast<char *>(ws);
+    SnapWs w;
+    w.res = reinterpret_cast<SnapRes *>(p);
+    p += 256;
+    w.cnt[0] = reinterpret_cast<uint32_t *>(p);
+    p += al256((size_t)(s->n_cust + 1) * 4);
+    w.cnt[1] = reinterpret_cast<uint32_t *>(p);
+    p += al256((size_t)(s->n_term + 1) * 4);
+    w.scan = p;
+    return w;
+}
+
+int resolve_sel(const fdx_key_selection *in, int64_t n_keys, const char *what, Sel *out) {
+    if (!in) {
+        *out = Sel{0, n_keys, 1};
+        return FDX_OK;
+    }
+    FDX_REQUIRE(in->first >= 0 && in->count >= 0 && in->step >= 1, "%s selection: first >= 0, count >= 0, step >= 1",
+                what);
+    FDX_REQUIRE(in->count == 0 || (in->first < n_keys && (in->count - 1) <= (n_keys - 1 - in->first) / in->step),
+                "%s selection (%lld, %lld, %lld) leaves the state's %lld keys", what, (long long)in->first,
+                (long long)in->count, (long long)in->step, (long long)n_keys);
+    *out = Sel{in->first, in->count, in->step};
+    return FDX_OK;
+}
+
+// The count pass of both halves; synchronises.  -> selections, totals and max_live on the host.
+int snap_count(fdx_stream s, const fdx_key_selection *csel, const fdx_key_selection *tsel, void *ws_d, size_t ws_bytes,
+               hipStream_t st, Sel sel[2], SnapRes *res_h) {
+    FDX_REQUIRE(s, "null stream state");
+    FDX_REQUIRE(ws_d && ws_bytes >= fdx_stream_snapshot_workspace_size(s), "workspace too small");
+    int rc;
+    if ((rc = resolve_sel(csel, s->n_cust, "customer", &sel[0]))) return rc;
+    if ((rc = resolve_sel(tsel, s->n_term, "terminal", &sel[1]))) return rc;
+    int32_t flags = 0;
+    FDX_HIP(hipMemcpyAsync(&flags, s->status_d, 4, hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    if (flags) {  // left set: the caller's fdx_stream_status still reports it
+        set_error("the stream state carries status bits %d (fdx_stream_status): not worth saving", flags);
+        return FDX_E_UNSUPPORTED;
+    }
+    const SnapWs w = snap_ws(s, ws_d);
+    FDX_HIP(hipMemsetAsync(w.res, 0, sizeof(SnapRes), st));
+    const Half h[2] = {cust_half(s), term_half(s)};
+    for (int i = 0; i < 2; ++i) {
+        hipLaunchKernelGGL(k_snap_count, dim3(stream_grid((sel[i].count + 1) << kCountShift, 256, 1024)), dim3(256), 0, st, h[i].state,
+                           h[i].R, h[i].pstride, (int64_t)h[i].ring_len, sel[i], w.cnt[i], w.res, i);
+        FDX_LAUNCHED("k_snap_count");
+        if ((rc = fdx_exclusive_scan_u32(w.cnt[i], sel[i].count + 1, w.scan, st))) return rc;
+    }
+    FDX_HIP(hipMemcpyAsync(res_h, w.res, sizeof(SnapRes), hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    if (res_h->bad) {
+        set_error("the %s state is inconsistent (a ring overflowed earlier?): not worth saving",
+                  res_h->bad & 1 ? "customer" : "terminal");
+        return FDX_E_UNSUPPORTED;
+    }
+    FDX_REQUIRE(res_h->total[0] < (1ull << 32) && res_h->total[1] < (1ull << 32),
+                "a half carries 2^32 or more ring entries: snapshot it in several key selections");
+    return FDX_OK;
+}
+
+}  // namespace
+}  // namespace fdx
+
+extern "C" size_t fdx_stream_snapshot_workspace_size(fdx_stream s) {
+    if (!s) return 0;
+    const int64_t m = (s->n_cust > s->n_term ? s->n_cust : s->n_term) + 1;
+    return 256 + al256((size_t)(s->n_cust + 1) * 4) + al256((size_t)(s->n_term + 1) * 4) +
+           fdx_exclusive_scan_u32_workspace_size(m) + 256;
+}
+
+extern "C" int fdx_stream_snapshot_size(fdx_stream s, const fdx_key_selection *customers,
+                                        const fdx_key_selection *terminals, size_t *bytes_h, void *workspace_d,
+                                        size_t workspace_bytes, void *stream) {
+    FDX_REQUIRE(bytes_h, "null pointer");
+    Sel sel[2];
+    SnapRes r;
+    const int rc = snap_count(s, customers, terminals, workspace_d, workspace_bytes, as_stream(stream), sel, &r);
+    if (rc) return rc;
+    uint64_t off[6], total;
+    snap_layout(s->W, (uint64_t)sel[0].count, r.total[0], (uint64_t)sel[1].count, r.total[1], off, &total);
+    *bytes_h = (size_t)total;
+    return FDX_OK;
+}
+
+extern "C" int fdx_stream_snapshot(fdx_stream s, const fdx_key_selection *customers,
+                                   const fdx_key_selection *terminals, void *snap_d, size_t snap_bytes,
+                                   size_t *written_h, void *workspace_d, size_t workspace_bytes, void *stream) {
+    FDX_REQUIRE(snap_d && ((uintptr_t)snap_d & 15) == 0, "snap_d must be a 16-byte aligned device pointer");
+    hipStream_t st = as_stream(stream);
+    Sel sel[2];
+    SnapRes r;
+    const int rc = snap_count(s, customers, terminals, workspace_d, workspace_bytes, st, sel, &r);
+    if (rc) return rc;
+    uint64_t off[6], total;
+    snap_layout(s->W, (uint64_t)sel[0].count, r.total[0], (uint64_t)sel[1].count, r.total[1], off, &total);
+    FDX_REQUIRE(snap_bytes >= total, "snapshot buffer of %zu bytes, the snapshot needs %llu", snap_bytes,
+                (unsigned long long)total);
+    const SnapWs w = snap_ws(s, workspace_d);
+    char *base = reinterpret_cast<char *>(snap_d);
+    auto words = [&](int sec) { return reinterpret_cast<int64_t *>(base + off[sec]); };
+    const Half hc = cust_half(s), ht = term_half(s);
+    if (sel[0].count) {
+        const int32_t sh = snap_gshift((int64_t)r.max_live[0]);
+        hipLaunchKernelGGL(k_snap_pack<CEnt>, dim3(group_grid(sel[0].count, sh)), dim3(256), 0, st, hc.state,
+                           s->cring_d, hc.R, hc.pstride, (int64_t)hc.ring_len, sel[0], w.cnt[0], words(0),
+                           words(1), reinterpret_cast<CEnt *>(base + off[2]), sh);
+        FDX_LAUNCHED("k_snap_pack");
+    }
+    if (sel[1].count) {
+        const int32_t sh = snap_gshift((int64_t)r.max_live[1]);
+        hipLaunchKernelGGL(k_snap_pack<int64_t>, dim3(group_grid(sel[1].count, sh)), dim3(256), 0, st, ht.state,
+                           s->tring_d, ht.R, ht.pstride, (int64_t)ht.ring_len, sel[1], w.cnt[1], words(3),
+                           words(4), words(5), sh);
+        FDX_LAUNCHED("k_snap_pack");
+    }
+    SnapHeader h{};
+    h.w[kHMagic] = (int64_t)kSnapMagic;
+    h.w[kHVersion] = kSnapVersion;
+    h.w[kHBytes] = (int64_t)total;
+    h.w[kHWindows] = s->W;
+    for (int i = 0; i < s->W; ++i) h.w[kHWin0 + i] = s->sw.win[i];
+    h.w[kHDelay] = s->sw.tb[0];
+    h.w[kHMode] = s->mode;
+    h.w[kHCRing] = s->C;
+    h.w[kHTRing] = s->T;
+    h.w[kHCKeys] = sel[0].count; h.w[kHCEntries] = (int64_t)r.total[0]; h.w[kHCMaxLive] = (int64_t)r.max_live[0];
+    h.w[kHTKeys] = sel[1].count; h.w[kHTEntries] = (int64_t)r.total[1]; h.w[kHTMaxLive] = (int64_t)r.max_live[1];
+    for (int i = 0; i < 6; ++i) h.w[kHOff + i] = (int64_t)off[i];
+    SnapTail t{};
+    auto put = [&](uint64_t byte, int64_t v) { t.word[t.n] = (int64_t)(byte / 8); t.value[t.n++] = v; };
+    put(off[1] + (uint64_t)sel[0].count * 8, (int64_t)r.total[0]);  // offsets[keys] = entries
+    if (!(sel[0].count & 1)) put(off[1] + (uint64_t)(sel[0].count + 1) * 8, 0);
+    put(off[4] + (uint64_t)sel[1].count * 8, (int64_t)r.total[1]);
+    if (!(sel[1].count & 1)) put(off[4] + (uint64_t)(sel[1].count + 1) * 8, 0);
+    if (r.total[1] & 1) put(off[5] + r.total[1] * 8, 0);
+    hipLaunchKernelGGL(k_snap_header, dim3(1), dim3(kHWords), 0, st, reinterpret_cast<int64_t *>(base), h, t,
+                       s->labels_d);
+    FDX_LAUNCHED("k_snap_header");
+    if (written_h) *written_h = (size_t)total;
+    return FDX_OK;
+}
+
+extern "C" int fdx_stream_snapshot_info(const void *header_h, size_t bytes, fdx_snapshot_info *out) {
+    FDX_REQUIRE(header_h && out, "null pointer");
+    FDX_REQUIRE(bytes >= (size_t)kHWords * 8, "%zu bytes are less than a snapshot header", bytes);
+    int64_t w[kHWords];
+    memcpy(w, header_h, sizeof(w));
+    FDX_REQUIRE((uint64_t)w[kHMagic] == kSnapMagic, "not a stream snapshot (magic)");
+    FDX_REQUIRE(w[kHVersion] == kSnapVersion, "snapshot format version %lld, this library reads %d",
+                (long long)w[kHVersion], kSnapVersion);
+    FDX_REQUIRE(w[kHBytes] >= 0 && (uint64_t)w[kHBytes] <= bytes, "the snapshot says %lld bytes, %zu are here",
+                (long long)w[kHBytes], bytes);
+    FDX_REQUIRE(w[kHWindows] >= 1 && w[kHWindows] <= kMaxW, "snapshot n_windows %lld outside [1, %d]",
+                (long long)w[kHWindows], kMaxW);
+    FDX_REQUIRE(w[kHCKeys] >= 0 && w[kHCKeys] <= INT32_MAX && w[kHTKeys] >= 0 && w[kHTKeys] <= INT32_MAX &&
+                    w[kHCEntries] >= 0 && w[kHCEntries] < (1ll << 32) && w[kHTEntries] >= 0 &&
+                    w[kHTEntries] < (1ll << 32),
+                "snapshot key or entry counts out of range");
+    FDX_REQUIRE((w[kHCKeys] || !w[kHCEntries]) && (w[kHTKeys] || !w[kHTEntries]), "snapshot entries without keys");
+    uint64_t off[6], total;
+    snap_layout((int)w[kHWindows], (uint64_t)w[kHCKeys], (uint64_t)w[kHCEntries], (uint64_t)w[kHTKeys],
+                (uint64_t)w[kHTEntries], off, &total);
+    for (int i = 0; i < 6; ++i)
+        FDX_REQUIRE((uint64_t)w[kHOff + i] == off[i], "snapshot section %d at byte %lld, the layout puts it at %llu", i,
+                    (long long)w[kHOff + i], (unsigned long long)off[i]);
+    FDX_REQUIRE((uint64_t)w[kHBytes] == total, "snapshot sections end at byte %llu, the header says %lld",
+                (unsigned long long)total, (long long)w[kHBytes]);
+    out->version = w[kHVersion];
+    out->total_bytes = w[kHBytes];
+    out->n_windows = w[kHWindows];
+    for (int i = 0; i < kMaxW; ++i) out->window_ns[i] = w[kHWin0 + i];
+    out->delay_ns = w[kHDelay];
+    out->flags_mode = w[kHMode];
+    out->customer_ring = w[kHCRing];
+    out->terminal_ring = w[kHTRing];
+    out->customer_keys = w[kHCKeys]; out->customer_entries = w[kHCEntries]; out->customer_max_live = w[kHCMaxLive];
+    out->terminal_keys = w[kHTKeys]; out->terminal_entries = w[kHTEntries]; out->terminal_max_live = w[kHTMaxLive];
+    for (int i = 0; i < kLabCounters; ++i) out->label_counts[i] = w[kHLabels + i];
+    for (int i = 0; i < 6; ++i) out->section_offset[i] = w[kHOff + i];
+    return FDX_OK;
+}
+
+extern "C" int fdx_stream_restore(fdx_stream s, const void *snap_d, size_t snap_bytes, int64_t customer_first,
+                                  int64_t customer_step, int64_t terminal_first, int64_t terminal_step, int32_t flags,
+                                  void *workspace_d, size_t workspace_bytes, void *stream) {
+    FDX_REQUIRE(s, "null stream state");
+    FDX_REQUIRE(snap_d && ((uintptr_t)snap_d & 15) == 0, "snap_d must be a 16-byte aligned device pointer");
+    FDX_REQUIRE((flags & ~FDX_RESTORE_COUNTERS) == 0, "unknown restore flags %d", flags);
+    FDX_REQUIRE(workspace_d && workspace_bytes >= 256, "workspace too small");
+    FDX_REQUIRE(snap_bytes >= (size_t)kHWords * 8, "%zu bytes are less than a snapshot header", snap_bytes);
+    hipStream_t st = as_stream(stream);
+    SnapHeader h;
+    FDX_HIP(hipMemcpyAsync(h.w, snap_d, sizeof(h.w), hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    fdx_snapshot_info f;
+    const int rc = fdx_stream_snapshot_info(h.w, snap_bytes, &f);
+    if (rc) return rc;
+    FDX_REQUIRE(f.n_windows == s->W, "the snapshot has %lld windows, the state %d", (long long)f.n_windows, s->W);
+    for (int i = 0; i < s->W; ++i)
+        FDX_REQUIRE(f.window_ns[i] == s->sw.win[i], "window %d: the snapshot has %lld ns, the state %lld", i,
+                    (long long)f.window_ns[i], (long long)s->sw.win[i]);
+    FDX_REQUIRE(f.delay_ns == s->sw.tb[0], "delay: the snapshot has %lld ns, the state %lld", (long long)f.delay_ns,
+                (long long)s->sw.tb[0]);
+    const Half half[2] = {cust_half(s), term_half(s)};
+    const int64_t keys[2] = {f.customer_keys, f.terminal_keys}, entries[2] = {f.customer_entries, f.terminal_entries};
+    const int64_t first[2] = {customer_first, terminal_first}, step[2] = {customer_step, terminal_step};
+    const int64_t max_live[2] = {f.customer_max_live, f.terminal_max_live};
+    const char *name[2] = {"customer", "terminal"};
+    for (int i = 0; i < 2; ++i) {
+        if (!keys[i]) continue;
+        FDX_REQUIRE(half[i].n_keys > 0, "the snapshot carries %s keys, the state has no %s half", name[i], name[i]);
+        FDX_REQUIRE(first[i] >= 0 && step[i] >= 1, "%s placement: first >= 0, step >= 1", name[i]);
+        FDX_REQUIRE(first[i] < half[i].n_keys && keys[i] - 1 <= (half[i].n_keys - 1 - first[i]) / step[i],
+                    "%s key %lld + %lld * %lld is beyond the state's capacity %lld", name[i], (long long)first[i],
+                    (long long)(keys[i] - 1), (long long)step[i], (long long)half[i].n_keys);
+    }
+    const char *base = reinterpret_cast<const char *>(snap_d);
+    auto words = [&](int sec) { return reinterpret_cast<const int64_t *>(base + f.section_offset[sec]); };
+    // pass 1, to completion before anything is written
+    SnapRes *res_d = reinterpret_cast<SnapRes *>(workspace_d), r;
+    memset(&r, 0, sizeof(r));
+    r.small[0] = r.small[1] = ~0ull;
+    FDX_HIP(hipMemcpyAsync(res_d, &r, sizeof(r), hipMemcpyHostToDevice, st));
+    for (int i = 0; i < 2; ++i) {
+        if (!keys[i]) continue;
+        hipLaunchKernelGGL(k_snap_validate, dim3((unsigned)ceil_div(keys[i], 256)), dim3(256), 0, st, words(3 * i),
+                           words(3 * i + 1), half[i].R, half[i].pstride, half[i].np, keys[i], entries[i],
+                           (int64_t)half[i].ring_len, res_d, i);
+        FDX_LAUNCHED("k_snap_validate");
+    }
+    FDX_HIP(hipMemcpyAsync(&r, res_d, sizeof(r), hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    FDX_REQUIRE(!r.bad, "the snapshot's %s offsets or pointers are malformed", r.bad & 1 ? "customer" : "terminal");
+    for (int i = 0; i < 2; ++i)
+        FDX_REQUIRE(r.small[i] == ~0ull, "%s key %lld has %llu live rows, the state's %s ring holds %d", name[i],
+                    (long long)(first[i] + (int64_t)(r.small[i] >> 32) * step[i]),
+                    (unsigned long long)(r.small[i] & 0xFFFFFFFFull), name[i], half[i].ring_len);
+    // pass 2
+    if (keys[0]) {
+        const int32_t sh = snap_gshift(max_live[0]);
+        hipLaunchKernelGGL(k_snap_unpack<CEnt>, dim3(group_grid(keys[0], sh)), dim3(256), 0, st, words(0), words(1),
+                           reinterpret_cast<const CEnt *>(base + f.section_offset[2]), half[0].R, keys[0], first[0],
+                           step[0], (int64_t)s->C, s->cstate_d, s->cring_d, sh);
+        FDX_LAUNCHED("k_snap_unpack");
+    }
+    if (keys[1]) {
+        const int32_t sh = snap_gshift(max_live[1]);
+        hipLaunchKernelGGL(k_snap_unpack<int64_t>, dim3(group_grid(keys[1], sh)), dim3(256), 0, st, words(3), words(4),
+                           words(5), half[1].R, keys[1], first[1], step[1], (int64_t)s->T, s->tstate_d, s->tring_d, sh);
+        FDX_LAUNCHED("k_snap_unpack");
+    }
+    if (flags & FDX_RESTORE_COUNTERS) {
+        hipLaunchKernelGGL(k_snap_add_labels, dim3(1), dim3(64), 0, st, s->labels_d, h);
+        FDX_LAUNCHED("k_snap_add_labels");
+    }
+    return FDX_OK;
+}

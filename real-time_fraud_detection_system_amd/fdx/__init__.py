@@ -23,6 +23,7 @@ from .evaluation import (card_precision_top_k, get_train_test_set, performance_a
                          performance_assessment_model_collection, pr_curve_points, roc_curve_points,
                          threshold_based_metrics)
 from .serving import customer_features_on, decode_cdc_batch, latest_terminal_features  # noqa: F401
+from .streaming import load_snapshot, save_snapshot, snapshot_info  # noqa: F401
 
 __all__ = ["is_weekend", "is_night", "get_customer_spending_behaviour_features",
            "get_count_risk_rolling_window", "scaleData", "fit_model_and_get_predictions",
@@ -30,4 +31,4 @@ __all__ = ["is_weekend", "is_night", "get_customer_spending_behaviour_features",
            "decode_cdc_batch", "get_train_test_set", "card_precision_top_k", "performance_assessment",
            "performance_assessment_model_collection", "threshold_based_metrics", "roc_curve_points",
            "pr_curve_points", "GpuForest", "INPUT_FEATURES", "FdxError", "FdxUnsupported",
-           "FDX_FLAGS_NOTEBOOK", "FDX_FLAGS_SPARK", "load"]
+           "FDX_FLAGS_NOTEBOOK", "FDX_FLAGS_SPARK", "load", "snapshot_info", "save_snapshot", "load_snapshot"]

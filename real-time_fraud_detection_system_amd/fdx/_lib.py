@@ -24,6 +24,8 @@ FDX_ROWS_SLOT_ORDER = 2   # ... by scoring slot (coalesced; each record carries 
 FDX_PREP_CUST_IN_TABLE = 32  # fdx_forest_prepare_grouped: the customer columns already sit in the table
 FDX_KEY_MOD, FDX_KEY_DIV, FDX_KEY_SUB = 0, 1, 2
 FDX_SELECT_LATEST, FDX_SELECT_FIRST_IN_RANGE = 0, 1  # fdx_table_select
+FDX_SNAPSHOT_HEADER_BYTES = 512
+FDX_RESTORE_COUNTERS = 1  # fdx_stream_restore's flags
 MAX_WINDOWS = 8
 MAX_FEATURES = 32
 
@@ -71,6 +73,20 @@ class RankingResult(ctypes.Structure):
                 ("auc_num", ctypes.c_uint64), ("auc", ctypes.c_double), ("ap", ctypes.c_double)]
 
 
+class KeySelection(ctypes.Structure):
+    """fdx_key_selection (include/fdx.h): keys first + j * step, j in [0, count)"""
+    _fields_ = [("first", c_i64), ("count", c_i64), ("step", c_i64)]
+
+
+class SnapshotInfo(ctypes.Structure):
+    """fdx_snapshot_info (include/fdx.h)"""
+    _fields_ = [("version", c_i64), ("total_bytes", c_i64), ("n_windows", c_i64), ("window_ns", c_i64 * MAX_WINDOWS),
+                ("delay_ns", c_i64), ("flags_mode", c_i64), ("customer_ring", c_i64), ("terminal_ring", c_i64),
+                ("customer_keys", c_i64), ("customer_entries", c_i64), ("customer_max_live", c_i64),
+                ("terminal_keys", c_i64), ("terminal_entries", c_i64), ("terminal_max_live", c_i64),
+                ("label_counts", c_i64 * 5), ("section_offset", c_i64 * 6)]
+
+
 # name -> (restype, argtypes); exactly the symbols declared in include/fdx.h
 SIGNATURES = {
     "fdx_last_error": (ctypes.c_char_p, []),
@@ -111,6 +127,13 @@ SIGNATURES = {
     "fdx_stream_report_frauds": (ctypes.c_int, [P, P, P, c_i64, P]),
     "fdx_stream_label_counts": (ctypes.c_int, [P, P, P]),
     "fdx_stream_destroy": (ctypes.c_int, [P]),
+    "fdx_stream_snapshot_workspace_size": (c_sz, [P]),
+    "fdx_stream_snapshot_size": (ctypes.c_int, [P, ctypes.POINTER(KeySelection), ctypes.POINTER(KeySelection), P, P,
+                                                c_sz, P]),
+    "fdx_stream_snapshot": (ctypes.c_int, [P, ctypes.POINTER(KeySelection), ctypes.POINTER(KeySelection), P, c_sz, P,
+                                           P, c_sz, P]),
+    "fdx_stream_snapshot_info": (ctypes.c_int, [P, c_sz, ctypes.POINTER(SnapshotInfo)]),
+    "fdx_stream_restore": (ctypes.c_int, [P, P, c_sz, c_i64, c_i64, c_i64, c_i64, c_i32, P, c_sz, P]),
     "fdx_train_test_split": (ctypes.c_int, [P, P, P, P, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, P, P, P,
                                             c_sz, P, P]),
     "fdx_card_precision_workspace_size": (ctypes.c_size_t, [c_i32]),

@@ -40,6 +40,59 @@ _STATUS = {1: "customer ring overflow (raise customer_ring)", 2: "terminal ring 
 LABEL_OUTCOMES = ("on_time", "late", "duplicate", "expired", "unmatched")  # fdx_stream_label_counts
 
 
+def _as_bytes_tensor(snap) -> torch.Tensor:
+    """A snapshot given as a tensor, a numpy array or bytes -> a flat uint8 tensor (where it lives)."""
+    if isinstance(snap, torch.Tensor):
+        t = snap
+    elif isinstance(snap, (bytes, bytearray, memoryview)):
+        t = torch.frombuffer(bytearray(snap), dtype=torch.uint8)
+    else:  # numpy
+        import numpy as np
+
+        t = torch.from_numpy(np.ascontiguousarray(snap).view(np.uint8).reshape(-1).copy())
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise FdxError("a snapshot is a contiguous uint8 buffer")
+    return t.reshape(-1)
+
+
+def _to_device_bytes(snap, device) -> torch.Tensor:
+    t = _as_bytes_tensor(snap)
+    return t if t.device.type == "cuda" else t.to(device)
+
+
+def snapshot_info(snap) -> dict:
+    """The checked header of a snapshot (device or host tensor, numpy array or bytes) as a dict:
+    version, total_bytes, window_ns, delay_ns, flags_mode, the source's customer_ring /
+    terminal_ring, per half keys / entries / max_live (the largest live row count of a key: a
+    ring must hold at least that), label_counts, section_offset.  Raises FdxError on anything
+    that is not a well-formed version-1 header."""
+    t = _as_bytes_tensor(snap)
+    head = bytes(t[:_lib.FDX_SNAPSHOT_HEADER_BYTES].cpu().numpy())
+    f = _lib.SnapshotInfo()
+    check(_lib.load().fdx_stream_snapshot_info(head, t.numel(), ctypes.byref(f)), "fdx_stream_snapshot_info")
+    d = {k: int(getattr(f, k)) for k, _ in _lib.SnapshotInfo._fields_ if k not in ("window_ns", "label_counts",
+                                                                                     "section_offset")}
+    d["window_ns"] = [int(w) for w in f.window_ns[:d["n_windows"]]]
+    d["label_counts"] = dict(zip(LABEL_OUTCOMES, (int(v) for v in f.label_counts)))
+    d["section_offset"] = [int(v) for v in f.section_offset]
+    return d
+
+
+def save_snapshot(path, snap) -> None:
+    """The snapshot's raw bytes to a file (no pickle)."""
+    _as_bytes_tensor(snap).cpu().numpy().tofile(path)
+
+
+def load_snapshot(path) -> torch.Tensor:
+    """-> the file's bytes as a pinned host uint8 tensor (StreamState.restore / from_snapshot take it)."""
+    import numpy as np
+
+    a = np.fromfile(path, dtype=np.uint8)
+    t = torch.empty(a.size, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    t.numpy()[:] = a
+    return t
+
+
 class StreamState:
     """Per-customer and per-terminal window state on the current GPU."""
 
@@ -59,6 +112,9 @@ class StreamState:
         b = ctypes.c_size_t()
         check(_lib.load().fdx_stream_memory(h, ctypes.byref(b)), "fdx_stream_memory")
         self.memory_bytes = b.value
+        self.n_customers, self.n_terminals = int(n_customers), int(n_terminals)
+        self.customer_ring, self.terminal_ring = int(customer_ring), int(terminal_ring)
+        self.delay_days, self.flags_mode = int(delay_days), int(flags_mode)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -131,6 +187,61 @@ class StreamState:
         check(_lib.load().fdx_stream_label_counts(self._h, c, ops._s(stream)), "fdx_stream_label_counts")
         return dict(zip(LABEL_OUTCOMES, (int(v) for v in c)))
 
+    def _snap_ws(self):
+        ws = getattr(self, "_snapshot_ws", None)
+        if ws is None:
+            ws = self._snapshot_ws = ops.workspace(_lib.load().fdx_stream_snapshot_workspace_size(self._h), self.device)
+        return ws
+
+    def snapshot(self, customers=None, terminals=None, stream=None) -> torch.Tensor:
+        """-> the live state as a device uint8 tensor (format: include/fdx.h; canonical bytes that
+        restore into any ring size and key capacity that fits).  customers / terminals: a key
+        selection (first, count, step) = keys first + j * step, j < count; None = every key.
+        Synchronises (a cold path); a state with a status bit up raises FdxUnsupported and the
+        bit stays up."""
+        L = _lib.load()
+        sel = [ctypes.byref(_lib.KeySelection(*(int(v) for v in s))) if s is not None else None
+               for s in (customers, terminals)]
+        ws = self._snap_ws()
+        nb = ctypes.c_size_t()
+        check(L.fdx_stream_snapshot_size(self._h, sel[0], sel[1], ctypes.byref(nb), ops._ptr(ws), ws.numel(),
+                                         ops._s(stream)), "fdx_stream_snapshot_size")
+        out = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
+        check(L.fdx_stream_snapshot(self._h, sel[0], sel[1], ops._ptr(out), out.numel(), None, ops._ptr(ws),
+                                    ws.numel(), ops._s(stream)), "fdx_stream_snapshot")
+        return out
+
+    def restore(self, snap, customers_at=(0, 1), terminals_at=(0, 1), counters=True, stream=None):
+        """Write a snapshot's keys into this state: snapshot key j lands on key first + j * step
+        (customers_at / terminals_at = (first, step)); all other keys are untouched, so restores
+        into disjoint key sets merge.  snap: device or host uint8 tensor, numpy array or bytes.
+        Refused (FdxError, nothing written) when the windows or the delay differ, a key falls
+        outside the capacity or a key's live rows exceed this state's ring.  counters: add the
+        snapshot's label counters to this state's.  State addresses do not move: a captured
+        score_graph stays valid."""
+        d = _to_device_bytes(snap, self.device)
+        ws = self._snap_ws()
+        check(_lib.load().fdx_stream_restore(self._h, ops._ptr(d), d.numel(), int(customers_at[0]),
+                                             int(customers_at[1]), int(terminals_at[0]), int(terminals_at[1]),
+                                             _lib.FDX_RESTORE_COUNTERS if counters else 0, ops._ptr(ws), ws.numel(),
+                                             ops._s(stream)), "fdx_stream_restore")
+
+    @classmethod
+    def from_snapshot(cls, snap, n_customers=None, n_terminals=None, customer_ring=None, terminal_ring=None,
+                      max_batch=65536):
+        """A new state holding the snapshot: windows, delay and flags mode from its header; key
+        capacities default to its key counts, ring sizes to those of its source."""
+        f = snapshot_info(snap)
+        if any(w % ops.NS_PER_DAY for w in f["window_ns"]) or f["delay_ns"] % ops.NS_PER_DAY:
+            raise FdxUnsupported("the snapshot's windows or delay are not whole days")
+        st = cls(f["customer_keys"] if n_customers is None else n_customers,
+                 f["terminal_keys"] if n_terminals is None else n_terminals,
+                 tuple(w // ops.NS_PER_DAY for w in f["window_ns"]), f["delay_ns"] // ops.NS_PER_DAY,
+                 f["customer_ring"] if customer_ring is None else customer_ring,
+                 f["terminal_ring"] if terminal_ring is None else terminal_ring, max_batch, f["flags_mode"])
+        st.restore(snap)
+        return st
+
     def check(self, stream=None):
         """Synchronise and raise if a kernel reported a problem since the last check."""
         f = ctypes.c_int32()
@@ -200,6 +311,18 @@ class StreamScorer:
         self.state.poll()
         self.state.report_frauds(ts, terminal)
         self.state.watch()
+
+    def snapshot(self, customers=None, terminals=None):
+        """StreamState.snapshot on the current stream, after the status of the batches so far
+        was waited for (a flagged batch raises here, as in finish())."""
+        self.state.poll(block=True)
+        return self.state.snapshot(customers, terminals)
+
+    def restore(self, snap, customers_at=(0, 1), terminals_at=(0, 1), counters=True):
+        """StreamState.restore on the current stream (status polled first).  The graphs captured
+        by score_graph stay valid: the state's addresses do not move."""
+        self.state.poll(block=True)
+        self.state.restore(snap, customers_at, terminals_at, counters)
 
     def score(self, ts, customer, amount, terminal, fraud=None):
         """-> predict_proba[:, 1] of the batch (device view, valid until the next call).
@@ -408,3 +531,15 @@ class ShardedStreamScorer:
 
     def finish(self):
         self.state.poll(block=True)
+
+    def snapshot(self, customers=None, terminals=None):
+        """This rank's state (its customer range and the terminals it owns, by local id);
+        rank-local, no collective.  To re-shard from N to M ranks, new rank r restores from
+        every old rank's snapshot the selection of the keys it will own."""
+        self.state.poll(block=True)
+        return self.state.snapshot(customers, terminals)
+
+    def restore(self, snap, customers_at=(0, 1), terminals_at=(0, 1), counters=True):
+        """StreamState.restore into this rank's state (local ids); rank-local, no collective."""
+        self.state.poll(block=True)
+        self.state.restore(snap, customers_at, terminals_at, counters)
