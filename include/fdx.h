@@ -868,7 +868,8 @@ int fdx_stream_restore(fdx_stream s, const void *snap_d, size_t snap_bytes, int6
  *   max(TX_FRAUD) over the day's rows of customers not yet detected; the top_k customers by
  *   (prediction desc, customer asc) that are compromised are detected (carried over when
  *   remove_detected); nb_compromised_h[k] = compromised customers of the day, cp_h[k] =
- *   detected / top_k.  Predictions must be >= 0.  The reference sorts with pandas' default
+ *   detected / top_k.  Predictions must be >= 0 and not NaN; -0.0 is accepted and ranks as
+ *   0.0 (the kernel canonicalises it before comparing).  The reference sorts with pandas' default
  *   (unstable) quicksort: equal predictions straddling the k-th place may order differently.
  *   workspace: fdx_card_precision_workspace_size(n_cust); one host sync per day. */
 int fdx_train_test_split(const int64_t *ts_d, const int32_t *day_d, const int32_t *cust_d, const uint8_t *fraud_d,

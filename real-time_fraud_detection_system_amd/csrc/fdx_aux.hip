@@ -243,7 +243,9 @@ __global__ void __launch_bounds__(256) k_split_pass3(const int32_t *__restrict__
 }
 
 // card_precision_top_k_day over the rows of one day, customers not yet detected:
-// per customer max(prediction) (order-preserving u64 keys; predictions are >= 0) and max(label)
+// per customer max(prediction) and max(label).  The maxima are taken on the doubles' bit patterns
+// (order-preserving for predictions >= 0); `+ 0.0` first turns -0.0 into +0.0, whose pattern
+// 0x8000... would otherwise rank above every positive prediction.
 __global__ void __launch_bounds__(256) k_cpk_day_max(const int32_t *__restrict__ day, const int32_t *__restrict__ cust,
                                                      const double *__restrict__ pred, const uint8_t *__restrict__ fraud,
                                                      int64_t n, int32_t d, const uint8_t *__restrict__ detected,
@@ -254,7 +256,7 @@ __global__ void __launch_bounds__(256) k_cpk_day_max(const int32_t *__restrict__
         const int32_t c = cust[i];
         if (detected[c]) continue;
         present[c] = 1;
-        atomicMax(&cmax[c], (unsigned long long)__double_as_longlong(pred[i]));
+        atomicMax(&cmax[c], (unsigned long long)__double_as_longlong(pred[i] + 0.0));
         if (fraud[i]) cfraud[c] = 1;
     }
 }
