@@ -24,7 +24,14 @@ restore into a second state of the same geometry are timed with HIP events, alte
 device-to-device copy of a buffer of the snapshot's size (the yardstick); the line gains a
 "snapshot" object.  The default line is unchanged.
 
+--late-terminals FRAC: a slow partition.  The customers whose id hashes below FRAC deliver the
+streamed day's rows one micro-batch late, so every customer's rows stay in time order while the
+terminals' do not; the scorer runs with terminal_lateness_days=1 (the late path of
+k_stream_process) and the line gains a "late_terminals" object with the two late-row counters.
+The default line is unchanged.
+
 usage: python bench_stream.py [--gpus N] [--batches K] [--warmup W] [--fraud-reports] [--snapshot]
+                              [--late-terminals FRAC]
 """
 import argparse
 import json
@@ -84,6 +91,28 @@ def _bit_length(c):
     return bl
 
 
+def hold_back(cols, h, bounds, frac):
+    """Reorder rows [h, n) of the columns `cols` (dict of numpy arrays in time order, changed in
+    place) as they arrive when the customers whose id hashes below `frac` deliver one batch late:
+    batch k = the held customers' rows of time slice k - 1, then the other customers' rows of
+    slice k (slices = `bounds`), plus one closing batch with the last slice's held rows.  Every
+    customer's rows stay in time order.  -> (new bounds, number of held rows)"""
+    import numpy as np
+
+    cust = cols["customer"][h:].astype(np.uint64)
+    slow = ((cust * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) < np.uint64(int(frac * 2 ** 32))
+    nb = len(bounds) - 1
+    batch = np.clip(np.searchsorted(bounds, np.arange(h, h + len(cust)), side="right") - 1, 0, nb - 1)
+    arrive = batch + slow
+    perm = np.argsort(arrive, kind="stable")
+    for k in cols:
+        cols[k][h:] = cols[k][h:][perm]
+    new = h + np.searchsorted(arrive[perm], np.arange(nb + 2))
+    if new[-1] == new[-2]:
+        new = new[:-1]
+    return new, int(slow.sum())
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -115,6 +144,10 @@ def parse(argv=None):
                     help="after the streamed day: time the state's snapshot and its restore into a second state "
                          "against a device-to-device copy of the same size (world 1)")
     ap.add_argument("--snapshot-repeats", type=int, default=10)
+    ap.add_argument("--late-terminals", type=float, default=0.0, metavar="FRAC",
+                    help="the customers whose id hashes below FRAC deliver the streamed day's rows one micro-batch "
+                         "late; the scorer runs with terminal_lateness_days=1 (world 1, not with --cdc or "
+                         "--fraud-reports)")
     return ap.parse_args(argv)
 
 
@@ -268,6 +301,11 @@ def main():
     cuts = cut_t.cpu().numpy()
     bounds = np.searchsorted(s_ts, cuts) + h
     bounds[0], bounds[-1] = h, len(d["ts"])
+    held = 0
+    if args.late_terminals > 0:
+        if world > 1 or args.cdc or args.fraud_reports:
+            raise SystemExit("--late-terminals runs at world 1 without --cdc and --fraud-reports")
+        bounds, held = hold_back(d, h, bounds, args.late_terminals)
     max_mb = int(np.diff(bounds).max())
     cap = max(max_day, max_mb, 1)
 
@@ -295,7 +333,8 @@ def main():
                                  terminal_ring=args.terminal_ring, max_batch=cap, max_recv=cap * world * 2)
     else:
         sc = StreamScorer(forest, n_c, args.terminals, customer_ring=args.customer_ring,
-                          terminal_ring=args.terminal_ring, max_batch=cap)
+                          terminal_ring=args.terminal_ring, max_batch=cap,
+                          terminal_lateness_days=1 if args.late_terminals > 0 else 0)
     cols = [("ts", torch.int64), ("customer", torch.int32), ("amount", torch.float64), ("terminal", torch.int32),
             ("fraud", torch.uint8)]
     reports = None
@@ -497,6 +536,11 @@ def main():
                     "report_unit": "ms (p50 device time of the report_frauds call before each timed batch; "
                                    "beside device_p50_ms)",
                     "mean_batch_reports": round(n_rep / max(n_timed, 1), 1), **counts})
+    if args.late_terminals > 0:
+        out["late_terminals"] = {"fraction": args.late_terminals, "held_rows": held, "terminal_lateness_days": 1,
+                                 **sc.state.late_counts(),
+                                 "what": "the held customers' rows arrive one micro-batch late; value / device_p50_ms "
+                                         "above are this run's (k_stream_process<W, true>)"}
     if args.snapshot:
         if world > 1:
             raise SystemExit("--snapshot runs at world 1")

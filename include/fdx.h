@@ -738,7 +738,30 @@ int fdx_cdc_compact(const uint8_t *keep_d, int64_t n, const int64_t *customer_d,
  *   cust_perm_d = NULL, term_inv_d = NULL, cust_ts_d / cust_amount_d = the batch's ts / amount).
  *   Asynchronous; errors inside the kernels are collected as bits:
  * fdx_stream_status: synchronises, returns and clears them (1 customer ring overflow, 2
- *   terminal ring overflow, 4 key out of range, 8 rows out of time order). */
+ *   terminal ring overflow, 4 key out of range, 8 rows out of time order, 16 a late terminal
+ *   row reaches past the ring).
+ * Late terminal rows (f-8).  A customer's rows come from one partition, in order; a terminal's
+ * come from every partition, so they may reach the state out of time order.
+ * fdx_stream_set_terminal_lateness(max_late_ns): 0 (the default) keeps the rule above for both
+ *   halves; negative is FDX_E_INVALID.  With max_late_ns > 0 a terminal's row may lie up to
+ *   max_late_ns before the terminal's latest row (the customer half stays strict: pandas'
+ *   roll_sum compensation words depend on the whole add / remove order).  Such a row gets the
+ *   counts of the rows that had arrived (arrival order: batch order, inside a batch (ts, row)
+ *   order) and is then inserted into the sorted ring after the rows with ts <= its own, and
+ *   every boundary that already lies past it gains it: the record and the live ring equal those
+ *   of a stream that had received the same rows in (ts, arrival) order.  The windows end
+ *   delay_ns before a row, so a row late by no more than delay_ns changes no feature of any row
+ *   and the stream stays bit-identical to the batch path over the sorted history.  Refused, with
+ *   zero counts for the row and nothing inserted: a row more than max_late_ns late (bit 8); a row
+ *   whose farthest window (t - delay_ns - the longest window) starts before the oldest row the
+ *   ring still holds (bit 16: raise terminal_ring) -- unless the terminal has had at most
+ *   terminal_ring rows and the state was never restored.  After fdx_stream_restore (until
+ *   fdx_stream_reset) only the oldest carried row's ts proves coverage: a snapshot carries the
+ *   same rows as before, those from the oldest boundary on.  The value is a kernel argument: a
+ *   captured graph of updates holds the value (and the restored flag) of its capture.
+ * fdx_stream_late_counts: counts_h = {late_rows (inserted), late_past_delay (inserted and
+ *   already behind the delay boundary: some feature emitted earlier lacked the row)};
+ *   synchronises; cumulative since create / reset; not part of a snapshot. */
 typedef struct fdx_stream_s *fdx_stream;
 int fdx_stream_create(int64_t n_customers, int64_t n_terminals, int32_t customer_ring, int32_t terminal_ring,
                       int32_t n_windows, const int64_t *window_ns, int64_t delay_ns, int32_t flags_mode,
@@ -749,6 +772,8 @@ int fdx_stream_update(fdx_stream s, const int64_t *ts_d, const int32_t *cust_d, 
                       const int32_t *term_d, const uint8_t *fraud_d, int64_t n, double *X_d, int64_t ld,
                       int32_t term_col0, int32_t *cust_nb_d, double *cust_sum_d, int64_t *term_rec_d,
                       void *stream);
+int fdx_stream_set_terminal_lateness(fdx_stream s, int64_t max_late_ns);
+int fdx_stream_late_counts(fdx_stream s, int64_t counts_h[2], void *stream);
 int fdx_stream_status(fdx_stream s, int32_t *flags_h, void *stream);
 /* Non-blocking form: enqueues the copy of the status bits to flags_pinned_h (pinned host
  * memory, valid once the stream reaches this point); does not clear them. */

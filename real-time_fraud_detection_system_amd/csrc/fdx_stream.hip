@@ -51,6 +51,17 @@ enum : int32_t {
     kStTermRing = 2,    // same for a terminal ring
     kStKey = 4,         // customer / terminal id outside [0, capacity)
     kStOrder = 8,       // a key's rows went back in time across batches
+    kStLateRing = 16,   // a late terminal row's farthest window reaches past the ring's live rows
+};
+
+// k_stream_process<W, LATE>'s extra arguments; none when LATE is false
+template <bool LATE>
+struct LateArgs {};
+template <>
+struct LateArgs<true> {
+    int64_t max_late;             // a terminal row may be this far (ns) behind the terminal's last row
+    int32_t strict;               // the state was restored: n <= T no longer proves the ring is whole
+    unsigned long long *counts;   // {late_rows, late_past_delay}
 };
 
 struct StreamWin {
@@ -243,12 +254,28 @@ __device__ void customer_key(int32_t c, int32_t head, const int32_t *__restrict_
     if (bad) atomicOr(status, bad);
 }
 
-template <int W>
+// Late terminal rows (f-8, LATE only).  chain_in_order visits a batch's rows in (ts, row) order,
+// so the rows older than the terminal's last row come first; each is handled on its own and
+// the in-order rows that follow take the unchanged path.
+//
+// Invariant: after a late row landed, the terminal's record and its live ring equal those of a
+// stream that had received the same rows in (ts, arrival) order.  The ring stays sorted: the
+// row is inserted after the rows with ts <= t (positions [q, n) move up by one), and a boundary
+// pointer p[k] counts the rows with ts <= last - tb[k], so it gains the row (and F[k] its fraud
+// bit) exactly when t <= last - tb[k].  The row's own features are counted over what had
+// arrived: pos_k = the live rows with ts <= t - tb[k] (binary search; pos_k <= p[k] because
+// t < last) and the fraud bits of [pos_k, p[k]) taken back out of F[k].  The windows end tb[0]
+// before a row, so a row late by no more than that delay changes no feature of any row.
+// Refused (status bit, zero counts, nothing inserted): a row more than max_late behind, and a
+// row whose farthest window starts before the ring's oldest live row -- unless the ring never
+// wrapped (n <= T) on a state that was never restored (a snapshot drops the rows before
+// min p[k], so after a restore only the oldest live row's ts proves coverage).
+template <int W, bool LATE>
 __device__ void terminal_key(int32_t tk, int32_t head, const int32_t *__restrict__ tnext,
                              const int64_t *__restrict__ ts, const uint8_t *__restrict__ fraud,
                              const StreamWin &sw, int64_t *__restrict__ tstate, int64_t *__restrict__ tring,
                              int32_t T, double *__restrict__ X, int64_t ld, int32_t tcol0, int64_t *__restrict__ rec_out,
-                             int32_t *__restrict__ status) {
+                             int32_t *__restrict__ status, const LateArgs<LATE> &la) {
     constexpr int K = W + 1;
     int64_t *rec = tstate + (int64_t)tk * (2 + 2 * K);
     int64_t *ring = tring + (int64_t)tk * T;
@@ -258,8 +285,78 @@ __device__ void terminal_key(int32_t tk, int32_t head, const int32_t *__restrict
 #pragma unroll
     for (int k = 0; k < K; ++k) { p[k] = rec[2 + 2 * k]; F[k] = rec[3 + 2 * k]; }
     int32_t bad = 0;
+    [[maybe_unused]] int32_t late_rows = 0, late_past = 0;
     chain_in_order(head, tnext, ts, [&](int32_t row, int64_t t) {
-        if (n > 0 && t < last) bad |= kStOrder;
+        if constexpr (LATE) {
+            if (n > 0 && t < last) {
+                const int64_t lo = n > T ? n - T : 0;  // live ring positions [lo, n), sorted by ts
+                auto upper = [&](int64_t bound) {      // the first live position with ts > bound
+                    int64_t a = lo, b = n;
+                    while (a < b) {
+                        const int64_t mid = (a + b) >> 1;
+                        if ((ring[mid & mask] >> 1) <= bound) a = mid + 1; else b = mid;
+                    }
+                    return a;
+                };
+                int32_t refused = 0;
+                if (last - t > la.max_late) {
+                    refused = kStOrder;
+                } else if (!((n <= T && !la.strict) || (ring[lo & mask] >> 1) <= t - sw.tb[W])) {
+                    refused = kStLateRing;
+                }
+                bad |= refused;
+                // the row's own counts, from what had arrived
+                int64_t pos[K], Fat[K];
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    pos[k] = 0; Fat[k] = 0;
+                    if (!refused) {
+                        pos[k] = upper(t - sw.tb[k]);
+                        Fat[k] = F[k];
+                        const int64_t pe = imin64(p[k], n);
+                        for (int64_t j = pos[k]; j < pe; ++j) Fat[k] -= ring[j & mask] & 1;
+                    }
+                }
+                // (the output forms of the in-order path, written out again: behind one shared helper
+                // the LATE = false kernel compiles to another register assignment, and it is to stay
+                // instruction for instruction the kernel it was before LATE existed)
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    const int32_t nb = (int32_t)(pos[0] - pos[w + 1]), fr = (int32_t)(Fat[0] - Fat[w + 1]);
+                    if (rec_out) {
+                        rec_out[(int64_t)row * W + w] = term_word(nb, fr);
+                    } else {
+                        double *x = X + (int64_t)row * ld + tcol0 + 2 * w;
+                        x[0] = (double)nb;
+                        x[1] = nb > 0 ? (double)fr / (double)nb : 0.0;
+                    }
+                }
+                if (refused) return;
+                // insertion after the rows with ts <= t: every later row moves up one position (a
+                // carry from the lowest, so a full ring drops its oldest row, as a push does)
+                const int64_t fbit = fraud[row] ? 1 : 0;
+                int64_t carry = (int64_t)(((uint64_t)t << 1) | (uint64_t)fbit);
+                for (int64_t j = upper(t); j < n; ++j) {
+                    const int64_t moved = ring[j & mask];
+                    ring[j & mask] = carry;
+                    carry = moved;
+                }
+                ring[n & mask] = carry;
+                int64_t pmin = n + 1;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {   // by the timestamps: q == p[k] happens either way
+                    if (t <= last - sw.tb[k]) { ++p[k]; F[k] += fbit; }
+                    pmin = p[k] < pmin ? p[k] : pmin;
+                }
+                if (n >= T && n - T >= pmin) bad |= kStTermRing;  // position n - T lost its slot
+                ++n;
+                ++late_rows;
+                late_past += t <= last - sw.tb[0];  // a feature already emitted lacked the row
+                return;
+            }
+        } else {
+            if (n > 0 && t < last) bad |= kStOrder;
+        }
         int64_t e[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) e[k] = p[k] < n ? ring[p[k] & mask] : INT64_MAX;
@@ -295,9 +392,15 @@ __device__ void terminal_key(int32_t tk, int32_t head, const int32_t *__restrict
 #pragma unroll
     for (int k = 0; k < K; ++k) { rec[2 + 2 * k] = p[k]; rec[3 + 2 * k] = F[k]; }
     if (bad) atomicOr(status, bad);
+    if constexpr (LATE) {
+        if (late_rows) atomicAdd(la.counts, (unsigned long long)late_rows);
+        if (late_past) atomicAdd(la.counts + 1, (unsigned long long)late_past);
+    }
 }
 
-template <int W>
+// LATE = false is the kernel of every state whose terminal lateness is 0 (the default): rows of
+// a key that go back in time raise kStOrder.  LATE = true is launched only with a lateness > 0.
+template <int W, bool LATE>
 __global__ void __launch_bounds__(256) k_stream_process(
     const int64_t *__restrict__ ts, const int32_t *__restrict__ cust, const double *__restrict__ amount,
     const int32_t *__restrict__ term, const uint8_t *__restrict__ fraud, int64_t n, int64_t n_cust, int64_t n_term,
@@ -305,7 +408,7 @@ __global__ void __launch_bounds__(256) k_stream_process(
     const int32_t *__restrict__ tnext, int64_t *__restrict__ cstate, CEnt *__restrict__ cring, int32_t C,
     int64_t *__restrict__ tstate, int64_t *__restrict__ tring, int32_t T, double *__restrict__ X, int64_t ld,
     int32_t tcol0, int32_t *__restrict__ cnb_out, double *__restrict__ csum_out, int64_t *__restrict__ rec_out,
-    int32_t *__restrict__ status) {
+    int32_t *__restrict__ status, LateArgs<LATE> la) {
     // grid.y = 2 when both halves run: the customer and terminal keys of a row are walked by
     // different threads, so their dependent-load chains overlap instead of adding up
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -323,7 +426,8 @@ __global__ void __launch_bounds__(256) k_stream_process(
     if (do_t) {
         const int32_t t = term[i];
         if (t >= 0 && t < n_term && thead[t] == (int32_t)i) {
-            terminal_key<W>(t, (int32_t)i, tnext, ts, fraud, sw, tstate, tring, T, X, ld, tcol0, rec_out, status);
+            terminal_key<W, LATE>(t, (int32_t)i, tnext, ts, fraud, sw, tstate, tring, T, X, ld, tcol0, rec_out, status,
+                                  la);
             thead[t] = -1;
         }
     }
@@ -420,6 +524,9 @@ struct fdx_stream_s {
     int64_t *cstate_d = nullptr, *tring_d = nullptr, *tstate_d = nullptr;
     int32_t *chead_d = nullptr, *thead_d = nullptr, *cnext_d = nullptr, *tnext_d = nullptr, *status_d = nullptr;
     unsigned long long *labels_d = nullptr;  // kLabCounters report outcomes since create / reset
+    unsigned long long *late_d = nullptr;    // {late_rows, late_past_delay} since create / reset
+    int64_t max_late = 0;                    // terminal lateness (ns); 0: rows must not go back in time
+    bool restored = false;                   // a restore wrote keys since create / reset (LateArgs::strict)
     size_t bytes = 0;
 };
 
@@ -440,6 +547,7 @@ extern "C" int fdx_stream_destroy(fdx_stream s) {
     (void)hipFree(s->tnext_d);
     (void)hipFree(s->status_d);
     (void)hipFree(s->labels_d);
+    (void)hipFree(s->late_d);
     delete s;
     return FDX_OK;
 }
@@ -457,6 +565,8 @@ extern "C" int fdx_stream_reset(fdx_stream s, void *stream) {
     }
     FDX_HIP(hipMemsetAsync(s->status_d, 0, 4, st));
     FDX_HIP(hipMemsetAsync(s->labels_d, 0, kLabCounters * 8, st));
+    FDX_HIP(hipMemsetAsync(s->late_d, 0, 2 * 8, st));
+    s->restored = false;
     return FDX_OK;
 }
 
@@ -501,7 +611,7 @@ extern "C" int fdx_stream_create(int64_t n_customers, int64_t n_terminals, int32
         (e = alloc((void **)&s->thead_d, nt * 4)) ||
         (e = alloc((void **)&s->cnext_d, (size_t)max_batch * 4)) ||
         (e = alloc((void **)&s->tnext_d, (size_t)max_batch * 4)) || (e = alloc((void **)&s->status_d, 4)) ||
-        (e = alloc((void **)&s->labels_d, kLabCounters * 8))) {
+        (e = alloc((void **)&s->labels_d, kLabCounters * 8)) || (e = alloc((void **)&s->late_d, 2 * 8))) {
         set_error("hipMalloc of the stream state (%zu bytes so far) failed: %s", s->bytes, hipGetErrorString(e));
         fdx_stream_destroy(s);
         return FDX_E_HIP;
@@ -521,12 +631,18 @@ extern "C" int fdx_stream_memory(fdx_stream s, size_t *bytes) {
     return FDX_OK;
 }
 
+#define FDX_STREAM_LAUNCH(WW, LATE, LA)                                                                          \
+    hipLaunchKernelGGL((k_stream_process<WW, LATE>), grid, dim3(256), 0, st, ts_d, cust_d, amount_d, term_d,     \
+                       fraud_d, n, s->n_cust, s->n_term, s->sw, s->chead_d, s->cnext_d, s->thead_d, s->tnext_d,  \
+                       s->cstate_d, s->cring_d, s->C, s->tstate_d, s->tring_d, s->T, X_d, ld, tcol, cust_nb_d,   \
+                       cust_sum_d, term_rec_d, s->status_d, LA)
 #define FDX_STREAM_PROCESS(WW)                                                                                   \
     case WW:                                                                                                     \
-        hipLaunchKernelGGL(k_stream_process<WW>, grid, dim3(256), 0, st, ts_d, cust_d, amount_d, term_d,         \
-                           fraud_d, n, s->n_cust, s->n_term, s->sw, s->chead_d, s->cnext_d, s->thead_d,          \
-                           s->tnext_d, s->cstate_d, s->cring_d, s->C, s->tstate_d, s->tring_d, s->T, X_d, ld,     \
-                           tcol, cust_nb_d, cust_sum_d, term_rec_d, s->status_d);                                \
+        if (late) {                                                                                              \
+            FDX_STREAM_LAUNCH(WW, true, la);                                                                     \
+        } else {                                                                                                 \
+            FDX_STREAM_LAUNCH(WW, false, LateArgs<false>{});                                                     \
+        }                                                                                                        \
         break;
 
 extern "C" int fdx_stream_update(fdx_stream s, const int64_t *ts_d, const int32_t *cust_d, const double *amount_d,
@@ -552,6 +668,8 @@ extern "C" int fdx_stream_update(fdx_stream s, const int64_t *ts_d, const int32_
                        s->status_d);
     FDX_LAUNCHED("k_stream_link");
     const dim3 grid((unsigned)ceil_div(n, 256), cust_d && term_d ? 2u : 1u);
+    const bool late = term_d && s->max_late > 0;
+    const LateArgs<true> la{s->max_late, s->restored ? 1 : 0, s->late_d};
     switch (W) {
         FDX_STREAM_PROCESS(1)
         FDX_STREAM_PROCESS(2)
@@ -605,6 +723,21 @@ extern "C" int fdx_stream_label_counts(fdx_stream s, int64_t counts_h[5], void *
     static_assert(kLabCounters == 5, "fdx.h documents five counters");
     hipStream_t st = as_stream(stream);
     FDX_HIP(hipMemcpyAsync(counts_h, s->labels_d, kLabCounters * 8, hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    return FDX_OK;
+}
+
+extern "C" int fdx_stream_set_terminal_lateness(fdx_stream s, int64_t max_late_ns) {
+    FDX_REQUIRE(s, "null stream state");
+    FDX_REQUIRE(max_late_ns >= 0, "negative terminal lateness");
+    s->max_late = max_late_ns;
+    return FDX_OK;
+}
+
+extern "C" int fdx_stream_late_counts(fdx_stream s, int64_t counts_h[2], void *stream) {
+    FDX_REQUIRE(s && counts_h, "null pointer");
+    hipStream_t st = as_stream(stream);
+    FDX_HIP(hipMemcpyAsync(counts_h, s->late_d, 2 * 8, hipMemcpyDeviceToHost, st));
     FDX_HIP(hipStreamSynchronize(st));
     return FDX_OK;
 }
@@ -1115,6 +1248,7 @@ extern "C" int fdx_stream_restore(fdx_stream s, const void *snap_d, size_t snap_
                     (long long)(first[i] + (int64_t)(r.small[i] >> 32) * step[i]),
                     (unsigned long long)(r.small[i] & 0xFFFFFFFFull), name[i], half[i].ring_len);
     // pass 2
+    s->restored = true;  // the carried rings start at min p[k]: late terminal rows take the strict rule
     if (keys[0]) {
         const int32_t sh = snap_gshift(max_live[0]);
         hipLaunchKernelGGL(k_snap_unpack<CEnt>, dim3(group_grid(keys[0], sh)), dim3(256), 0, st, words(0), words(1),

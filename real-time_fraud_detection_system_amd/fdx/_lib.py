@@ -122,6 +122,8 @@ SIGNATURES = {
     "fdx_stream_reset": (ctypes.c_int, [P, P]),
     "fdx_stream_memory": (ctypes.c_int, [P, P]),
     "fdx_stream_update": (ctypes.c_int, [P, P, P, P, P, P, c_i64, P, c_i64, c_i32, P, P, P, P]),
+    "fdx_stream_set_terminal_lateness": (ctypes.c_int, [P, c_i64]),
+    "fdx_stream_late_counts": (ctypes.c_int, [P, P, P]),
     "fdx_stream_status": (ctypes.c_int, [P, P, P]),
     "fdx_stream_status_async": (ctypes.c_int, [P, P, P]),
     "fdx_stream_report_frauds": (ctypes.c_int, [P, P, P, c_i64, P]),

@@ -36,8 +36,10 @@ from . import _lib, ops
 from ._lib import FdxError, FdxUnsupported, check
 
 _STATUS = {1: "customer ring overflow (raise customer_ring)", 2: "terminal ring overflow (raise terminal_ring)",
-           4: "customer or terminal id outside the state's capacity", 8: "a key's rows went back in time"}
+           4: "customer or terminal id outside the state's capacity", 8: "a key's rows went back in time",
+           16: "a late terminal row reaches past the ring (raise terminal_ring)"}
 LABEL_OUTCOMES = ("on_time", "late", "duplicate", "expired", "unmatched")  # fdx_stream_label_counts
+LATE_COUNTS = ("late_rows", "late_past_delay")  # fdx_stream_late_counts
 
 
 def _as_bytes_tensor(snap) -> torch.Tensor:
@@ -98,7 +100,9 @@ class StreamState:
 
     def __init__(self, n_customers: int, n_terminals: int, windows_days=(1, 7, 30), delay_days=7,
                  customer_ring=256, terminal_ring=256, max_batch=65536, flags_mode=_lib.FDX_FLAGS_NOTEBOOK,
-                 stream=None):
+                 stream=None, terminal_lateness_days=0):
+        """terminal_lateness_days (fractions allowed; 0 = off): how far a terminal's row may lie
+        behind the terminal's latest row (set_terminal_lateness)."""
         self.device = ops.require_gpu()
         self.windows_days = tuple(int(d) for d in windows_days)
         self.W = len(self.windows_days)
@@ -115,6 +119,27 @@ class StreamState:
         self.n_customers, self.n_terminals = int(n_customers), int(n_terminals)
         self.customer_ring, self.terminal_ring = int(customer_ring), int(terminal_ring)
         self.delay_days, self.flags_mode = int(delay_days), int(flags_mode)
+        self.terminal_lateness_ns, self.restored = 0, False
+        if terminal_lateness_days:
+            self.set_terminal_lateness(terminal_lateness_days)
+
+    def set_terminal_lateness(self, days):
+        """Accept terminal rows up to `days` (fractions allowed) behind their terminal's latest
+        row: they get the counts of what had arrived and land in the state as if they had come
+        in order (include/fdx.h: the refusals, status bits 8 and 16).  Rows late by no more than
+        the delay change no feature of any row.  0 = off: any row that goes back in time raises.
+        The customer half stays strict.  The value is a kernel argument: graphs captured by
+        StreamScorer.score_graph are keyed by it."""
+        ns = int(round(float(days) * ops.NS_PER_DAY))
+        check(_lib.load().fdx_stream_set_terminal_lateness(self._h, ns), "fdx_stream_set_terminal_lateness")
+        self.terminal_lateness_ns = ns
+
+    def late_counts(self, stream=None) -> dict:
+        """Synchronise; -> {late_rows: late terminal rows inserted, late_past_delay: those already
+        behind the delay boundary (an earlier row's features lacked them)} since create / reset."""
+        c = (ctypes.c_int64 * len(LATE_COUNTS))()
+        check(_lib.load().fdx_stream_late_counts(self._h, c, ops._s(stream)), "fdx_stream_late_counts")
+        return dict(zip(LATE_COUNTS, (int(v) for v in c)))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -124,6 +149,7 @@ class StreamState:
 
     def reset(self, stream=None):
         check(_lib.load().fdx_stream_reset(self._h, ops._s(stream)), "fdx_stream_reset")
+        self.restored = False
 
     def update(self, ts, customer=None, amount=None, terminal=None, fraud=None, X=None, term_col0=-1,
                term_records=None, cust_nb=None, cust_sum=None, stream=None):
@@ -218,19 +244,23 @@ class StreamState:
         Refused (FdxError, nothing written) when the windows or the delay differ, a key falls
         outside the capacity or a key's live rows exceed this state's ring.  counters: add the
         snapshot's label counters to this state's.  State addresses do not move: a captured
-        score_graph stays valid."""
+        score_graph stays valid.  A snapshot carries a key's rows from its oldest boundary on, so
+        from here until reset() a late terminal row is accepted only when the oldest row the ring
+        holds reaches the row's farthest window (else status bit 16)."""
         d = _to_device_bytes(snap, self.device)
         ws = self._snap_ws()
         check(_lib.load().fdx_stream_restore(self._h, ops._ptr(d), d.numel(), int(customers_at[0]),
                                              int(customers_at[1]), int(terminals_at[0]), int(terminals_at[1]),
                                              _lib.FDX_RESTORE_COUNTERS if counters else 0, ops._ptr(ws), ws.numel(),
                                              ops._s(stream)), "fdx_stream_restore")
+        self.restored = True
 
     @classmethod
     def from_snapshot(cls, snap, n_customers=None, n_terminals=None, customer_ring=None, terminal_ring=None,
-                      max_batch=65536):
+                      max_batch=65536, terminal_lateness_days=0):
         """A new state holding the snapshot: windows, delay and flags mode from its header; key
-        capacities default to its key counts, ring sizes to those of its source."""
+        capacities default to its key counts, ring sizes to those of its source.  The terminal
+        lateness is no part of a snapshot: pass it again."""
         f = snapshot_info(snap)
         if any(w % ops.NS_PER_DAY for w in f["window_ns"]) or f["delay_ns"] % ops.NS_PER_DAY:
             raise FdxUnsupported("the snapshot's windows or delay are not whole days")
@@ -238,7 +268,8 @@ class StreamState:
                  f["terminal_keys"] if n_terminals is None else n_terminals,
                  tuple(w // ops.NS_PER_DAY for w in f["window_ns"]), f["delay_ns"] // ops.NS_PER_DAY,
                  f["customer_ring"] if customer_ring is None else customer_ring,
-                 f["terminal_ring"] if terminal_ring is None else terminal_ring, max_batch, f["flags_mode"])
+                 f["terminal_ring"] if terminal_ring is None else terminal_ring, max_batch, f["flags_mode"],
+                 terminal_lateness_days=terminal_lateness_days)
         st.restore(snap)
         return st
 
@@ -278,10 +309,10 @@ class StreamScorer:
 
     def __init__(self, forest: ops.Forest, n_customers: int, n_terminals: int, windows_days=(1, 7, 30),
                  delay_days=7, customer_ring=256, terminal_ring=256, max_batch=65536,
-                 flags_mode=_lib.FDX_FLAGS_NOTEBOOK, fused=True):
+                 flags_mode=_lib.FDX_FLAGS_NOTEBOOK, fused=True, terminal_lateness_days=0):
         self.forest = forest
         self.state = StreamState(n_customers, n_terminals, windows_days, delay_days, customer_ring, terminal_ring,
-                                 max_batch, flags_mode)
+                                 max_batch, flags_mode, terminal_lateness_days=terminal_lateness_days)
         W = self.state.W
         if forest.n_features != 3 + 4 * W:
             raise FdxError(f"forest has {forest.n_features} features, the stream makes {3 + 4 * W}")
@@ -304,6 +335,14 @@ class StreamScorer:
         if z is None:
             z = self._zero_fraud = torch.zeros(self.state.max_batch, dtype=torch.uint8, device=self.state.device)
         return z[:n]
+
+    def set_terminal_lateness(self, days):
+        """StreamState.set_terminal_lateness; a change drops the graphs score_graph captured (the
+        value is an argument of the kernels inside them)."""
+        before = self.state.terminal_lateness_ns
+        self.state.set_terminal_lateness(days)
+        if self.state.terminal_lateness_ns != before:
+            self.__dict__.pop("_graphs", None)
 
     def report_frauds(self, ts, terminal):
         """StreamState.report_frauds on the current stream, with score()'s status polling (a
@@ -372,6 +411,8 @@ class StreamScorer:
             fraud = self._no_labels(n)
         key = (n, self.forest.epoch) + tuple(t.data_ptr() for t in (ts, customer, amount, terminal, fraud)) + \
             ((out_host.data_ptr(),) if out_host is not None else ())
+        if self.state.terminal_lateness_ns:  # the late kernel's arguments: the lateness, the restored flag
+            key += ("late", self.state.terminal_lateness_ns, self.state.restored)
         graphs = self.__dict__.setdefault("_graphs", {})
         g = graphs.get(key)
         if g is None:
@@ -486,14 +527,18 @@ class ShardedStreamScorer:
     def __init__(self, forest: ops.Forest, world: int, rank: int, n_customers_local: int, customer_base: int,
                  n_terminals_total: int, windows_days=(1, 7, 30), delay_days=7, customer_ring=256,
                  terminal_ring=256, max_batch=65536, max_recv=None, flags_mode=_lib.FDX_FLAGS_NOTEBOOK,
-                 group=None):
+                 group=None, terminal_lateness_days=0):
+        """terminal_lateness_days: the owner-side terminal state accepts rows that late (the
+        ranks' batches of one terminal need not be aligned in time); the customer half stays
+        strict.  Not yet run on more than one GPU with a lateness set."""
         self.forest, self.world, self.rank, self.group = forest, world, rank, group
         self.customer_base = int(customer_base)
         self.n_terminals_total = int(n_terminals_total)
         n_term_local = (self.n_terminals_total + world - 1) // world
         # the owner side sees up to every rank's rows of its terminals in one batch
         self.state = StreamState(n_customers_local, n_term_local, windows_days, delay_days, customer_ring,
-                                 terminal_ring, max(max_batch, max_recv or max_batch * world), flags_mode)
+                                 terminal_ring, max(max_batch, max_recv or max_batch * world), flags_mode,
+                                 terminal_lateness_days=terminal_lateness_days)
         self.windows_days, self.delay_days = self.state.windows_days, int(delay_days)
         W = self.state.W
         dev = self.state.device
