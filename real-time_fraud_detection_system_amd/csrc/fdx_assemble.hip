@@ -276,32 +276,6 @@ __global__ void __launch_bounds__(256) k_scale(const double *__restrict__ X, int
     }
 }
 
-// The weekend / night flags of a nanosecond timestamp, with the floor divisions of pandas'
-// dt accessors (feature_transformation.ipynb's is_weekend / is_night; fraud_detection.py's
-// dayofweek / hour for FDX_FLAGS_SPARK).  floor(t / 1 day) = floor(floor(t / 1 s) / 86,400 s) and
-// the hour likewise, so one 64-bit division to whole seconds, then 32-bit day / hour / weekday
-// arithmetic while the seconds fit (1901-2038), the 64-bit form otherwise: the same values.
-__device__ __forceinline__ void day_flags(int64_t t, int32_t flags_mode, bool &we, bool &ni) {
-    int64_t sec = t / 1000000000LL;
-    if (sec * 1000000000LL != t && t < 0) --sec;
-    int32_t hour, wd;
-    if (sec >= INT32_MIN && sec <= INT32_MAX) {
-        const int32_t s32 = (int32_t)sec;
-        int32_t day = s32 / 86400;
-        if (day * 86400 != s32 && s32 < 0) --day;
-        hour = (s32 - day * 86400) / 3600;
-        wd = (day + 3) % 7;
-    } else {
-        int64_t day = sec / 86400;
-        if (day * 86400 != sec && sec < 0) --day;
-        hour = (int32_t)((sec - day * 86400) / 3600);
-        wd = (int32_t)((day + 3) % 7);
-    }
-    if (wd < 0) wd += 7;
-    we = flags_mode == FDX_FLAGS_NOTEBOOK ? wd >= 5 : (((wd + 1) % 7) + 1) >= 5;
-    ni = flags_mode == FDX_FLAGS_NOTEBOOK ? hour <= 6 : hour >= 20;
-}
-
 __device__ __forceinline__ float zval(double x, const double *mean, const double *scale, int f) {
     if (mean) x = x - mean[f];
     if (scale) x = x / scale[f];

@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "fdx.h"
 
@@ -85,8 +86,109 @@ __device__ __forceinline__ void compact_load(const int64_t *rec, int64_t q, int6
     }
 }
 
+// pandas roll_sum state (aggregations.pyx add_sum/remove_sum/calc_sum), emulated exactly: the
+// batch windows (fdx_windows.hip) and the streaming state (fdx_stream.hip) run this one copy.
+struct RollSum {
+    double sum, c_add, c_rem, prev;
+    int32_t nobs, nsame;
+
+    __device__ __forceinline__ void reset(double first) {
+        sum = 0.0; c_add = 0.0; c_rem = 0.0; prev = first; nobs = 0; nsame = 0;
+    }
+    __device__ __forceinline__ void add(double v) {
+        if (v == v) {
+            nobs += 1;
+            double y = v - c_add;
+            double t = sum + y;
+            c_add = (t - sum) - y;
+            sum = t;
+            nsame = (v == prev) ? nsame + 1 : 1;
+            prev = v;
+        }
+    }
+    __device__ __forceinline__ void remove(double v) {
+        if (v == v) {
+            nobs -= 1;
+            double y = -v - c_rem;
+            double t = sum + y;
+            c_rem = (t - sum) - y;
+            sum = t;
+        }
+    }
+    // calc_sum with min_periods = 1 (offset windows)
+    __device__ __forceinline__ double value() const {
+        if (nobs >= 1) return (nsame >= nobs) ? prev * (double)nobs : sum;
+        return __builtin_nan("");
+    }
+};
+
+constexpr int64_t kNsPerSec = 1000000000LL;
+constexpr int32_t kSecPerDay = 86400, kSecPerHour = 3600;
+
+// The weekend / night flags of a nanosecond timestamp, with the floor divisions of pandas'
+// dt accessors (feature_transformation.ipynb's is_weekend / is_night; fraud_detection.py's
+// dayofweek / hour for FDX_FLAGS_SPARK).  floor(t / 1 day) = floor(floor(t / 1 s) / 86,400 s) and
+// the hour likewise, so one 64-bit division to whole seconds, then 32-bit day / hour / weekday
+// arithmetic while the seconds fit (1901-2038), the 64-bit form otherwise: the same values.
+__device__ __forceinline__ void day_flags(int64_t t, int32_t flags_mode, bool &we, bool &ni) {
+    int64_t sec = t / kNsPerSec;
+    if (sec * kNsPerSec != t && t < 0) --sec;
+    int32_t hour, wd;
+    if (sec >= INT32_MIN && sec <= INT32_MAX) {
+        const int32_t s32 = (int32_t)sec;
+        int32_t day = s32 / kSecPerDay;
+        if (day * kSecPerDay != s32 && s32 < 0) --day;
+        hour = (s32 - day * kSecPerDay) / kSecPerHour;
+        wd = (day + 3) % 7;  // Monday = 0 (1970-01-01 was a Thursday); day may be < 0
+    } else {
+        int64_t day = sec / kSecPerDay;
+        if (day * kSecPerDay != sec && sec < 0) --day;
+        hour = (int32_t)((sec - day * kSecPerDay) / kSecPerHour);
+        wd = (int32_t)((day + 3) % 7);
+    }
+    if (wd < 0) wd += 7;
+    // Spark dayofweek: Sunday = 1 .. Saturday = 7
+    we = flags_mode == FDX_FLAGS_NOTEBOOK ? wd >= 5 : (((wd + 1) % 7) + 1) >= 5;
+    ni = flags_mode == FDX_FLAGS_NOTEBOOK ? hour <= 6 : hour >= 20;
+}
+
+// Inclusive scan (sum) across the wave; lane = the thread's lane.
+template <class T>
+__device__ __forceinline__ T wave_incl_scan(T v, int lane) {
+    // __shfl_up has no uint64_t overload: 8-byte integers travel as unsigned long long
+    using S = std::conditional_t<std::is_integral<T>::value && sizeof(T) == 8, unsigned long long, T>;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const T u = (T)__shfl_up((S)v, d, kWave);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
+// Exclusive scan of one value per thread over a block of WAVES waves; *total = the block's sum.
+// Its own barriers on both sides of the LDS use, so calls may follow each other.
+template <int WAVES, class T>
+__device__ __forceinline__ T block_excl_scan(T v, T *total) {
+    __shared__ T s_w[WAVES];
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+    const T inc = wave_incl_scan(v, lane);
+    if (lane == kWave - 1) s_w[wv] = inc;
+    __syncthreads();
+    T base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const T x = s_w[w];
+        if (w < wv) base += x;
+        tot += x;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t round_up(size_t a, size_t m) { return (a + m - 1) / m * m; }
+inline size_t al256(size_t x) { return round_up(x, 256); }  // workspace carve-outs: 256-byte aligned
 
 // Grid for a grid-stride streaming kernel: enough blocks to fill 256 CUs several times,
 // capped so launch overhead and tail stay small (cdna_hip_programming.md Guideline 11).

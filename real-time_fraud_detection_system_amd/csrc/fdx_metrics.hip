@@ -54,35 +54,6 @@ __global__ void __launch_bounds__(kMBlock) k_score_keys(const double *__restrict
         atomicAdd(reinterpret_cast<unsigned long long *>(&res->n_nonfinite), (unsigned long long)bad);
 }
 
-// ---- u64 block scan / sums (integer: any order gives the same bits)
-__device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t u = __shfl_up((unsigned long long)v, d, kWave);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
-// exclusive block scan of one value per thread; *total = the block's sum
-__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint64_t *total) {
-    __shared__ uint64_t s_w[kMWaves];
-    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-    const uint64_t inc = wave_incl_scan_u64(v, lane);
-    if (lane == kWave - 1) s_w[wv] = inc;
-    __syncthreads();
-    uint64_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kMWaves; ++w) {
-        const uint64_t x = s_w[w];
-        if (w < wv) base += x;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 // The scanned element of sorted position i: (i starts a group) << 32 | (label of the row).
 __device__ __forceinline__ uint64_t pair_of(bool starts, uint32_t val) {
     return ((uint64_t)(starts ? 1u : 0u) << 32) | (val >> 31);
@@ -100,7 +71,7 @@ __global__ void __launch_bounds__(kMBlock) k_group_partials(const uint64_t *__re
         if (i < n) s += pair_of(i == 0 || sk[i] != sk[i - 1], vals[i]);
     }
     uint64_t tot;
-    block_excl_scan_u64(s, &tot);
+    block_excl_scan<kMWaves>(s, &tot);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -111,7 +82,7 @@ __global__ void __launch_bounds__(kMBlock) k_part_scan(uint64_t *__restrict__ pa
         const int64_t i = c + threadIdx.x;
         const uint64_t v = i < P ? part[i] : 0ull;
         uint64_t tot;
-        const uint64_t ex = block_excl_scan_u64(v, &tot);
+        const uint64_t ex = block_excl_scan<kMWaves>(v, &tot);
         if (i < P) part[i] = ex + carry;
         carry += tot;
     }
@@ -142,7 +113,7 @@ __global__ void __launch_bounds__(kMBlock) k_group_ends(const uint64_t *__restri
         if (i < n) s += pair_of(i == 0 || key[k + 1] != key[k], val[k]);
     }
     uint64_t tot;
-    uint64_t run = block_excl_scan_u64(s, &tot) + part[blockIdx.x];
+    uint64_t run = block_excl_scan<kMWaves>(s, &tot) + part[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kMItems; ++k) {
         const int64_t i = i0 + k;

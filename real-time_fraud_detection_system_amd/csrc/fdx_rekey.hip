@@ -29,34 +29,7 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kScanBlock = 256;
 constexpr int kScanItems = 16;
 constexpr int kScanChunk = kScanBlock * kScanItems;
-
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        uint32_t u = __shfl_up(v, d, kWave);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
-// exclusive block scan of one value per thread; returns the block total via *total
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *total) {
-    __shared__ uint32_t s_w[kScanBlock / kWave];
-    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-    uint32_t inc = wave_incl_scan_u32(v, lane);
-    if (lane == kWave - 1) s_w[wv] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kScanBlock / kWave; ++w) {
-        uint32_t x = s_w[w];
-        if (w < wv) base += x;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
+constexpr int kScanWaves = kScanBlock / kWave;
 
 __global__ void __launch_bounds__(kScanBlock) k_scan_partials(const uint32_t *__restrict__ in,
                                                               int64_t m, uint32_t *__restrict__ part) {
@@ -68,7 +41,7 @@ __global__ void __launch_bounds__(kScanBlock) k_scan_partials(const uint32_t *__
         if (i < m) s += in[i];
     }
     uint32_t tot;
-    block_excl_scan(s, &tot);
+    block_excl_scan<kScanWaves>(s, &tot);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -79,7 +52,7 @@ __global__ void __launch_bounds__(kScanBlock) k_scan_single(uint32_t *__restrict
         int64_t i = c + threadIdx.x;
         uint32_t v = i < P ? part[i] : 0u;
         uint32_t tot;
-        uint32_t ex = block_excl_scan(v, &tot);
+        uint32_t ex = block_excl_scan<kScanWaves>(v, &tot);
         if (i < P) part[i] = ex + carry;
         carry += tot;
     }
@@ -99,7 +72,7 @@ __global__ void __launch_bounds__(kScanBlock) k_scan_apply(const uint32_t *in, i
         s += v[k];
     }
     uint32_t tot;
-    uint32_t ex = block_excl_scan(s, &tot) + part[blockIdx.x];
+    uint32_t ex = block_excl_scan<kScanWaves>(s, &tot) + part[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kScanItems; ++k) {
         int64_t i = base + k;
@@ -229,7 +202,6 @@ inline unsigned scatter_grid(int64_t n_tiles) { return (unsigned)((n_tiles + 7) 
 // stream 1 stays an 8-byte stream (unchecked) in every pass.
 enum { kPayWide = 0, kPayConvert = 1, kPayNarrow = 2, kPayWideGated = 3 };
 constexpr unsigned kGatedGrid = 2048;  // blocks of a kPayWideGated launch (a multiple of 8)
-constexpr int64_t kNsPerSec = 1000000000LL;
 
 // int32 seconds relative to base, exact iff ts - base is a whole number of seconds that fits
 __device__ __forceinline__ uint32_t narrow_ts(uint64_t bits, int64_t base, bool *ok) {
@@ -395,7 +367,7 @@ __device__ __forceinline__ void scatter_one_tile(
             sum += tot_d[q];
         }
         uint32_t tot;
-        uint32_t ex = block_excl_scan(sum, &tot);  // (its own barriers: every s_cnt read above is done)
+        uint32_t ex = block_excl_scan<kScanWaves>(sum, &tot);  // (its own barriers: every s_cnt read above is done)
 #pragma unroll
         for (int q = 0; q < kPer; ++q) {
             const int d = tid * kPer + q;

@@ -6,7 +6,7 @@
 // call over the concatenated history (tests/test_gpu_stream.py):
 //   customer (feature_transformation.ipynb:601-628): per window the pandas roll_sum state
 //     (sum, Kahan add/remove compensations, nobs, n-same run, prev -- aggregations.pyx
-//     add_sum/remove_sum/calc_sum, see RollSum in fdx_windows.hip) and the window's tail
+//     add_sum/remove_sum/calc_sum, see RollSum in fdx_internal.h) and the window's tail
 //     (pandas' variable-window start), plus a ring of the customer's recent (ts, amount) rows
 //     from which the tails remove;
 //   terminal (:1495-1522): per window boundary (delay, delay + w) the count of the terminal's
@@ -43,8 +43,6 @@ namespace fdx {
 namespace {
 
 constexpr int kMaxW = FDX_MAX_WINDOWS;
-constexpr int64_t kNsPerDay = 86400LL * 1000000000LL;
-constexpr int64_t kNsPerHour = 3600LL * 1000000000LL;
 
 enum : int32_t {
     kStCustRing = 1,    // a customer ring slot still inside a window was overwritten
@@ -74,51 +72,6 @@ struct alignas(16) CEnt {
     double amt;
 };
 
-// pandas roll_sum (aggregations.pyx add_sum / remove_sum / calc_sum), same as fdx_windows.hip
-struct Roll {
-    double sum, c_add, c_rem, prev;
-    int32_t nobs, nsame;
-    __device__ __forceinline__ void reset(double first) {
-        sum = 0.0; c_add = 0.0; c_rem = 0.0; prev = first; nobs = 0; nsame = 0;
-    }
-    __device__ __forceinline__ void add(double v) {
-        if (v == v) {
-            nobs += 1;
-            double y = v - c_add, t = sum + y;
-            c_add = (t - sum) - y;
-            sum = t;
-            nsame = (v == prev) ? nsame + 1 : 1;
-            prev = v;
-        }
-    }
-    __device__ __forceinline__ void remove(double v) {
-        if (v == v) {
-            nobs -= 1;
-            double y = -v - c_rem, t = sum + y;
-            c_rem = (t - sum) - y;
-            sum = t;
-        }
-    }
-    __device__ __forceinline__ double value() const {
-        if (nobs >= 1) return (nsame >= nobs) ? prev * (double)nobs : sum;
-        return __builtin_nan("");
-    }
-};
-
-__device__ __forceinline__ void time_flags(int64_t t, int32_t mode, double &we, double &ni) {
-    int64_t day = t / kNsPerDay;
-    if (t % kNsPerDay != 0 && t < 0) --day;
-    const int64_t hour = (t - day * kNsPerDay) / kNsPerHour;
-    int64_t wd = (day + 3) % 7;  // Monday = 0 (1970-01-01 was a Thursday)
-    if (wd < 0) wd += 7;
-    if (mode == FDX_FLAGS_NOTEBOOK) {
-        we = wd >= 5; ni = hour <= 6;
-    } else {
-        const int64_t dow = ((wd + 1) % 7) + 1;  // Spark dayofweek: Sunday = 1 .. Saturday = 7
-        we = dow >= 5; ni = hour >= 20;
-    }
-}
-
 __global__ void __launch_bounds__(256) k_stream_link(
     const int64_t *__restrict__ ts, const int32_t *__restrict__ cust, const double *__restrict__ amount,
     const int32_t *__restrict__ term, int64_t n, int64_t n_cust, int64_t n_term, int32_t *__restrict__ chead,
@@ -133,8 +86,8 @@ __global__ void __launch_bounds__(256) k_stream_link(
                 cnext[i] = atomicExch(&chead[c], (int32_t)i);
             }
             if (X) {
-                double we, ni;
-                time_flags(ts[i], mode, we, ni);
+                bool we, ni;
+                day_flags(ts[i], mode, we, ni);
                 double *x = X + i * ld;
                 x[0] = amount[i]; x[1] = we; x[2] = ni;
             }
@@ -188,7 +141,7 @@ __device__ void customer_key(int32_t c, int32_t head, const int32_t *__restrict_
     const int64_t mask = C - 1;
     int64_t n = rec[0], last = rec[1];
     int64_t tail[W];
-    Roll s[W];
+    RollSum s[W];
 #pragma unroll
     for (int w = 0; w < W; ++w) {
         const int64_t *r = rec + 2 + 6 * w;
@@ -975,7 +928,6 @@ __global__ void __launch_bounds__(64) k_snap_add_labels(unsigned long long *__re
     if (threadIdx.x < kLabCounters) labels[threadIdx.x] += (unsigned long long)h.w[kHLabels + threadIdx.x];
 }
 
-size_t al256(size_t b) { return round_up(b, 256); }
 
 // Lanes per key: 16, the fastest of 4 .. 64 at config 5 (58 live rows per customer on average,
 // 160 at most: profiles/stream_snapshot.json; a group covering the longest run, 64, was the

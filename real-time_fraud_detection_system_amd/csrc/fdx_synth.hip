@@ -240,7 +240,6 @@ __global__ void __launch_bounds__(256) k_synth_emit(const int32_t *__restrict__ 
     }
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int check_desc(const fdx_synth_desc *s) {
     FDX_REQUIRE(s, "null descriptor");

@@ -14,15 +14,29 @@
 namespace fdx {
 namespace {
 
-constexpr int64_t kNsPerDay = 86400LL * 1000000000LL;
-constexpr int64_t kNsPerHour = 3600LL * 1000000000LL;
-
-__device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {
-    int64_t q = a / b;
-    return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
+// ----------------------------------------------------------------------------- flags
+// k_time_flags keeps the 64-bit day / hour form of day_flags (fdx_internal.h; the same values,
+// tests/test_gpu_flag_edges.py holds the two together).  With day_flags, whose int32 and 64-bit
+// regimes are both expanded behind a per-row branch in each of the 8 unrolled rows (912 -> 1432
+// static instructions), the kernel measured 0.0694-0.0699 ms against 0.0675-0.0680 ms on the
+// bench's 17.8M rows: 0.002 ms slower, the parent-vs-parent spread of that run being 0.0005 ms.
+constexpr int64_t kNsPerDay = kSecPerDay * kNsPerSec, kNsPerHour = kSecPerHour * kNsPerSec;
+__device__ __forceinline__ void day_flags_ns(int64_t t, int32_t mode, bool &we, bool &ni) {
+    int64_t day = t / kNsPerDay;
+    if (t % kNsPerDay != 0 && t < 0) --day;
+    const int64_t hour = (t - day * kNsPerDay) / kNsPerHour;
+    int64_t wd = (day + 3) % 7;  // Monday = 0 (1970-01-01 was a Thursday); day may be < 0
+    if (wd < 0) wd += 7;
+    if (mode == FDX_FLAGS_NOTEBOOK) {
+        we = wd >= 5;
+        ni = hour <= 6;
+    } else {
+        const int64_t dow = ((wd + 1) % 7) + 1;  // Spark dayofweek: Sunday = 1 .. Saturday = 7
+        we = dow >= 5;
+        ni = hour >= 20;
+    }
 }
 
-// ----------------------------------------------------------------------------- flags
 // 8 rows per thread: 64 B of timestamps in, 8 B per flag array out (one u64 store each).
 __global__ void __launch_bounds__(256) k_time_flags(const int64_t *__restrict__ ts, int64_t n,
                                                     int32_t mode, uint8_t *__restrict__ weekend,
@@ -34,20 +48,8 @@ __global__ void __launch_bounds__(256) k_time_flags(const int64_t *__restrict__ 
         uint64_t we = 0, ni = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            int64_t t = p[k];
-            int64_t day = floor_div(t, kNsPerDay);
-            int64_t hour = (t - day * kNsPerDay) / kNsPerHour;
-            int64_t wd = (day + 3) % 7;  // Monday=0 (1970-01-01 was a Thursday); day may be < 0
-            if (wd < 0) wd += 7;
             bool w, nt;
-            if (mode == FDX_FLAGS_NOTEBOOK) {
-                w = wd >= 5;
-                nt = hour <= 6;
-            } else {
-                int64_t dow = ((wd + 1) % 7) + 1;  // Spark dayofweek: Sunday=1 .. Saturday=7
-                w = dow >= 5;
-                nt = hour >= 20;
-            }
+            day_flags_ns(p[k], mode, w, nt);
             we |= (uint64_t)w << (8 * k);
             ni |= (uint64_t)nt << (8 * k);
         }
@@ -56,61 +58,17 @@ __global__ void __launch_bounds__(256) k_time_flags(const int64_t *__restrict__ 
     }
     // tail (< 8 rows) handled by block 0
     if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - n8 * 8)) {
-        int64_t i = n8 * 8 + threadIdx.x;
-        int64_t t = ts[i];
-        int64_t day = floor_div(t, kNsPerDay);
-        int64_t hour = (t - day * kNsPerDay) / kNsPerHour;
-        int64_t wd = (day + 3) % 7;
-        if (wd < 0) wd += 7;
-        if (mode == FDX_FLAGS_NOTEBOOK) {
-            weekend[i] = wd >= 5;
-            night[i] = hour <= 6;
-        } else {
-            int64_t dow = ((wd + 1) % 7) + 1;
-            weekend[i] = dow >= 5;
-            night[i] = hour >= 20;
-        }
+        const int64_t i = n8 * 8 + threadIdx.x;
+        bool w, nt;
+        day_flags_ns(ts[i], mode, w, nt);
+        weekend[i] = w;
+        night[i] = nt;
     }
 }
 
 // ------------------------------------------------------------------ customer windows
 struct WinArgs {
     int64_t w[FDX_MAX_WINDOWS];
-};
-
-// pandas roll_sum state (aggregations.pyx add_sum/remove_sum/calc_sum), emulated exactly.
-struct RollSum {
-    double sum, c_add, c_rem, prev;
-    int32_t nobs, nsame;
-
-    __device__ __forceinline__ void reset(double first) {
-        sum = 0.0; c_add = 0.0; c_rem = 0.0; prev = first; nobs = 0; nsame = 0;
-    }
-    __device__ __forceinline__ void add(double v) {
-        if (v == v) {
-            nobs += 1;
-            double y = v - c_add;
-            double t = sum + y;
-            c_add = (t - sum) - y;
-            sum = t;
-            nsame = (v == prev) ? nsame + 1 : 1;
-            prev = v;
-        }
-    }
-    __device__ __forceinline__ void remove(double v) {
-        if (v == v) {
-            nobs -= 1;
-            double y = -v - c_rem;
-            double t = sum + y;
-            c_rem = (t - sum) - y;
-            sum = t;
-        }
-    }
-    // calc_sum with min_periods = 1 (offset windows)
-    __device__ __forceinline__ double value() const {
-        if (nobs >= 1) return (nsame >= nobs) ? prev * (double)nobs : sum;
-        return __builtin_nan("");
-    }
 };
 
 // One lane per (segment, window).  The lane walks its segment in time order with a tail
@@ -351,12 +309,7 @@ __global__ void __launch_bounds__(kPlanWaves * kWave) k_layout_plan_small(const 
     uint32_t gs = 0;
     for (int64_t g = g0; g < g1; ++g) gs += s_gs[g];
     // (a wave scan, then the 16 wave totals: 1 barrier instead of 20)
-    uint32_t inc = gs;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, kWave);
-        if (lane >= d) inc += t;
-    }
+    const uint32_t inc = wave_incl_scan(gs, lane);
     if (lane == kWave - 1) s_part[wv] = inc;
     __syncthreads();
     uint32_t wsum = 0;
@@ -392,7 +345,6 @@ __global__ void __launch_bounds__(kPlanWaves * kWave) k_layout_plan_small(const 
 // columns; flag raised, the columns are the 8-byte ones.  A uniform branch around the loads.
 // NAMT = false: only ts has a narrow form, amount is the float64 column (FDX_NARROW_TS alone).
 constexpr int kStartLds = 1024;  // segment rows staged per wave for the start searches
-constexpr int64_t kNsPerSec = 1000000000LL;
 // interleave_groups is the block's work; k_interleave (8-byte columns) and k_interleave_narrow are
 // its kernels.
 template <bool STARTS, bool GROUPED, bool NARROW, bool NAMT>
@@ -1115,15 +1067,8 @@ __global__ void __launch_bounds__(64) k_customer_scan(
                         c = 1;
                     }
                 }
-#pragma unroll
-                for (int d = 1; d < kWave; d <<= 1) {
-                    const double u = __shfl_up(v, d, kWave);
-                    const int32_t uc = __shfl_up(c, d, kWave);
-                    if (lane >= d) {
-                        v += u;
-                        c += uc;
-                    }
-                }
+                v = wave_incl_scan(v, lane);
+                c = wave_incl_scan(c, lane);
                 const double e = carry + v;
                 const int32_t cc = ccarry + c;
                 if (t < L) {
@@ -1198,15 +1143,8 @@ __global__ void __launch_bounds__(256) k_seg_prefix(const double *__restrict__ g
                     c = 1;
                 }
             }
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const double u = __shfl_up(v, d, kWave);
-                const int32_t uc = __shfl_up(c, d, kWave);
-                if (lane >= d) {
-                    v += u;
-                    c += uc;
-                }
-            }
+            v = wave_incl_scan(v, lane);
+            c = wave_incl_scan(c, lane);
             const double e = carry + v;
             const int32_t cc = ccarry + c;
             if (t < L) {
@@ -1258,16 +1196,6 @@ constexpr int kTermLdsRows = 1024;  // rows of one segment staged per wave (12 K
 // stage (3 KB per wave instead of 12: about twice the resident waves for this latency-bound
 // kernel), the longer ones in a second launch with the full stage (see terminal_launch).
 constexpr int kTermShortRows = 256;
-
-
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        int u = __shfl_up(v, d, kWave);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
 
 // Output either column-major (nb_out/risk_out [W][n], grouped order) or, when rec_out !=
 // nullptr, one count record per row (W words NB | FRAUD << 32, see fdx.h) at rec_out[row].
@@ -1982,8 +1910,6 @@ extern "C" int fdx_assemble_features(int64_t n, int32_t n_windows, const double 
     return FDX_OK;
 }
 
-static size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
 extern "C" size_t fdx_customer_layout_workspace_size(int64_t n_seg) {
     if (n_seg < 0) n_seg = 0;
     return al256((size_t)n_seg * 4) + al256((size_t)(65535 + 2) * 8) + fdx_rekey_workspace_size(n_seg, 16) +
@@ -2228,6 +2154,47 @@ static int fork_stream(ForkStream **out) {
     return FDX_OK;
 }
 
+// The host side of the walk for both entry points below; strided = none, or the one
+// WalkStrided<AVG> that k_customer_walk takes behind lg_max.
+// Length classes: the groups of the longest segments (the busiest customers, whose
+// longest window holds more rows than the 128-row ring minus a chunk, so nearly every
+// removal would miss the ring and wait on a dependent global load) walk with a 256-row
+// ring on a forked stream, concurrently with the rest on the 128-row ring (twice the
+// blocks per CU); the class boundary is kWalkSplitRows.
+// buf: buffer stores, for outputs that fit 2^31 bytes (raw buffer offsets are 32-bit).
+template <class... Strided>
+static int walk_launch(const double *iamt_d, const int64_t *seg_off_d, const int32_t *sorder_d, const uint32_t *goff_d,
+                       int64_t n_seg, int64_t n_slots, int32_t n_windows, const int32_t *starts_d, int32_t *nb_d,
+                       double *val_d, bool buf, hipStream_t st, Strided... strided) {
+    const int32_t S = kWave / n_windows;
+    FDX_REQUIRE(S <= 21, "the walk kernel is built for <= 21 segments per wave (>= 3 windows)");
+    const int64_t n_groups = ceil_div(n_seg, S);
+    const char *name = sizeof...(Strided) ? "k_customer_walk<WalkStrided>" : "k_customer_walk";
+    ForkStream *f;
+    int rc = fork_stream(&f);
+    if (rc) return rc;
+    FDX_HIP(hipEventRecord(f->fork, st));
+    FDX_HIP(hipStreamWaitEvent(f->side, f->fork, 0));
+    auto classes = [&](auto b) -> int {
+        constexpr bool BUF = decltype(b)::value;
+        constexpr int PL = kWalkLongWaves, PS = kWalkShortWaves;
+        hipLaunchKernelGGL((k_customer_walk<(21 + PL - 1) / PL, 256, PL, BUF, kWalkChunk, Strided...>),
+                           dim3((unsigned)(n_groups * PL)), dim3(64), 0, f->side, iamt_d, seg_off_d, sorder_d, goff_d,
+                           n_seg, S, n_slots, n_windows, nb_d, val_d, starts_d, kWalkSplitRows, INT32_MAX, strided...);
+        FDX_LAUNCHED(name);
+        hipLaunchKernelGGL((k_customer_walk<(21 + PS - 1) / PS, 128, PS, BUF, kWalkChunk, Strided...>),
+                           dim3((unsigned)(n_groups * PS)), dim3(64), 0, st, iamt_d, seg_off_d, sorder_d, goff_d, n_seg,
+                           S, n_slots, n_windows, nb_d, val_d, starts_d, 0, kWalkSplitRows, strided...);
+        FDX_LAUNCHED(name);
+        return FDX_OK;
+    };
+    rc = buf ? classes(std::true_type{}) : classes(std::false_type{});
+    if (rc) return rc;
+    FDX_HIP(hipEventRecord(f->join, f->side));
+    FDX_HIP(hipStreamWaitEvent(st, f->join, 0));
+    return FDX_OK;
+}
+
 extern "C" int fdx_customer_windows_walk(const double *iamt_d, const int64_t *seg_off_d, const int32_t *sorder_d,
                                          const uint32_t *goff_d, int64_t n_seg, int64_t n_slots, int32_t n_windows,
                                          const int32_t *starts_d, int32_t *nb_d, double *sum_d, void *stream) {
@@ -2235,39 +2202,10 @@ extern "C" int fdx_customer_windows_walk(const double *iamt_d, const int64_t *se
     FDX_REQUIRE(n_windows >= 1 && n_windows <= FDX_MAX_WINDOWS, "bad n_windows");
     if (n_seg == 0) return FDX_OK;
     FDX_REQUIRE(iamt_d && seg_off_d && sorder_d && goff_d && starts_d && nb_d && sum_d, "null pointer");
-    const int32_t S = kWave / n_windows;
-    FDX_REQUIRE(S <= 21, "the walk kernel is built for <= 21 segments per wave (>= 3 windows)");
-    const int64_t n_groups = ceil_div(n_seg, S);
-    hipStream_t st = as_stream(stream);
-    // Length classes: the groups of the longest segments (the busiest customers, whose
-    // longest window holds more rows than the 128-row ring minus a chunk, so nearly every
-    // removal would miss the ring and wait on a dependent global load) walk with a 256-row
-    // ring on a forked stream, concurrently with the rest on the 128-row ring (twice the
-    // blocks per CU); the class boundary is kWalkSplitRows.
-    constexpr int split = kWalkSplitRows;
-    // buffer stores while the outputs fit 2^31 bytes (raw buffer offsets are 32-bit)
+    // buffer stores while the outputs fit 2^31 bytes
     const bool buf = (int64_t)n_windows * n_slots * 8 < (int64_t)INT32_MAX / 8 * 8;
-#define FDX_WALK(SM, RING, P, STREAM, LO, HI)                                                                 \
-    if (buf)                                                                                                  \
-        hipLaunchKernelGGL((k_customer_walk<SM, RING, P, true, kWalkChunk>), dim3((unsigned)(n_groups * (P))), dim3(64), 0, \
-                           STREAM, iamt_d, seg_off_d, sorder_d, goff_d, n_seg, S, n_slots, n_windows, nb_d, sum_d, \
-                           starts_d, LO, HI);                                                                  \
-    else                                                                                                      \
-        hipLaunchKernelGGL((k_customer_walk<SM, RING, P, false, kWalkChunk>), dim3((unsigned)(n_groups * (P))), dim3(64), 0, \
-                           STREAM, iamt_d, seg_off_d, sorder_d, goff_d, n_seg, S, n_slots, n_windows, nb_d, sum_d, \
-                           starts_d, LO, HI);                                                                  \
-    FDX_LAUNCHED("k_customer_walk")
-    ForkStream *f;
-    int rc = fork_stream(&f);
-    if (rc) return rc;
-    FDX_HIP(hipEventRecord(f->fork, st));
-    FDX_HIP(hipStreamWaitEvent(f->side, f->fork, 0));
-    FDX_WALK((21 + kWalkLongWaves - 1) / kWalkLongWaves, 256, kWalkLongWaves, f->side, split, INT32_MAX);
-    FDX_WALK((21 + kWalkShortWaves - 1) / kWalkShortWaves, 128, kWalkShortWaves, st, 0, split);
-    FDX_HIP(hipEventRecord(f->join, f->side));
-    FDX_HIP(hipStreamWaitEvent(st, f->join, 0));
-    return FDX_OK;
-#undef FDX_WALK
+    return walk_launch(iamt_d, seg_off_d, sorder_d, goff_d, n_seg, n_slots, n_windows, starts_d, nb_d, sum_d, buf,
+                       as_stream(stream));
 }
 
 extern "C" int fdx_customer_windows_walk_strided(const double *iamt_d, const int64_t *seg_off_d,
@@ -2281,40 +2219,14 @@ extern "C" int fdx_customer_windows_walk_strided(const double *iamt_d, const int
                 (long long)nb_stride, (long long)val_stride, (long long)n_slots);
     if (n_seg == 0) return FDX_OK;
     FDX_REQUIRE(iamt_d && seg_off_d && sorder_d && goff_d && starts_d && nb_d && val_d, "null pointer");
-    const int32_t S = kWave / n_windows;
-    FDX_REQUIRE(S <= 21, "the walk kernel is built for <= 21 segments per wave (>= 3 windows)");
-    const int64_t n_groups = ceil_div(n_seg, S);
-    hipStream_t st = as_stream(stream);
-    constexpr int split = kWalkSplitRows;  // the length classes of fdx_customer_windows_walk
-    // buffer stores while the strided outputs fit 2^31 bytes (raw buffer offsets are 32-bit)
+    // buffer stores while the strided outputs fit 2^31 bytes
     const int64_t smax = nb_stride > val_stride ? nb_stride : val_stride;
     const bool buf = (int64_t)n_windows * smax * 8 < (int64_t)INT32_MAX / 8 * 8;
-    const bool avg = val_is_avg != 0;
-#define FDX_WALK_K(SM, RING, P, B, A, STREAM, LO, HI)                                                          \
-    hipLaunchKernelGGL((k_customer_walk<SM, RING, P, B, kWalkChunk, WalkStrided<A>>), dim3((unsigned)(n_groups * (P))), \
-                       dim3(64), 0, STREAM, iamt_d, seg_off_d, sorder_d, goff_d, n_seg, S, n_slots, n_windows, nb_d, \
-                       val_d, starts_d, LO, HI, WalkStrided<A>{nb_stride, val_stride})
-#define FDX_WALK(SM, RING, P, STREAM, LO, HI)                                                                  \
-    if (buf) {                                                                                                 \
-        if (avg) FDX_WALK_K(SM, RING, P, true, true, STREAM, LO, HI);                                          \
-        else FDX_WALK_K(SM, RING, P, true, false, STREAM, LO, HI);                                             \
-    } else {                                                                                                   \
-        if (avg) FDX_WALK_K(SM, RING, P, false, true, STREAM, LO, HI);                                         \
-        else FDX_WALK_K(SM, RING, P, false, false, STREAM, LO, HI);                                            \
-    }                                                                                                          \
-    FDX_LAUNCHED("k_customer_walk<WalkStrided>")
-    ForkStream *f;
-    int rc = fork_stream(&f);
-    if (rc) return rc;
-    FDX_HIP(hipEventRecord(f->fork, st));
-    FDX_HIP(hipStreamWaitEvent(f->side, f->fork, 0));
-    FDX_WALK((21 + kWalkLongWaves - 1) / kWalkLongWaves, 256, kWalkLongWaves, f->side, split, INT32_MAX);
-    FDX_WALK((21 + kWalkShortWaves - 1) / kWalkShortWaves, 128, kWalkShortWaves, st, 0, split);
-    FDX_HIP(hipEventRecord(f->join, f->side));
-    FDX_HIP(hipStreamWaitEvent(st, f->join, 0));
-    return FDX_OK;
-#undef FDX_WALK
-#undef FDX_WALK_K
+    auto go = [&](auto strided) {
+        return walk_launch(iamt_d, seg_off_d, sorder_d, goff_d, n_seg, n_slots, n_windows, starts_d, nb_d, val_d, buf,
+                           as_stream(stream), strided);
+    };
+    return val_is_avg ? go(WalkStrided<true>{nb_stride, val_stride}) : go(WalkStrided<false>{nb_stride, val_stride});
 }
 
 extern "C" int fdx_customer_windows_interleaved(const int64_t *its_d, const double *iamt_d,
