@@ -113,6 +113,23 @@ def hold_back(cols, h, bounds, frac):
     return new, int(slow.sum())
 
 
+RAW_ID_SCRAMBLE = {"customer": (0x9E3779B1, 1 << 41), "terminal": (0x85EBCA6B, 1 << 42)}  # (odd multiplier, offset)
+
+
+def raw_id_scramble(ids, mult, offset):
+    """--raw-ids: dense ids -> raw 64-bit ids, id * mult + offset in int64.  Injective (no
+    wrap-around: 0 <= id < 2^31 and mult < 2^32 keep the product under 2^63) and above 2^40
+    (offset), so nothing about the values is dense, sorted by arrival or fits int32."""
+    import numpy as np
+
+    ids = np.asarray(ids)
+    if mult % 2 == 0 or not 0 < mult < 2 ** 32 or not 2 ** 40 < offset < 2 ** 62:
+        raise ValueError("the scramble needs an odd 32-bit multiplier and an offset in (2^40, 2^62)")
+    if ids.size and (ids.min() < 0 or ids.max() >= 2 ** 31):
+        raise ValueError("ids must lie in [0, 2^31)")
+    return ids.astype(np.int64) * np.int64(mult) + np.int64(offset)
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -148,6 +165,11 @@ def parse(argv=None):
                     help="the customers whose id hashes below FRAC deliver the streamed day's rows one micro-batch "
                          "late; the scorer runs with terminal_lateness_days=1 (world 1, not with --cdc or "
                          "--fraud-reports)")
+    ap.add_argument("--raw-ids", action="store_true",
+                    help="the same table with customer / terminal ids scrambled to raw 64-bit values "
+                         "(raw_id_scramble) into a StreamScorer(raw_ids=True): the key directories map them "
+                         "inside the batch's graph.  A dense scorer runs beside it up to the first timed "
+                         "batch, whose probabilities must be bit-identical (raw_ids_match_dense)")
     return ap.parse_args(argv)
 
 
@@ -308,6 +330,13 @@ def main():
         bounds, held = hold_back(d, h, bounds, args.late_terminals)
     max_mb = int(np.diff(bounds).max())
     cap = max(max_day, max_mb, 1)
+    dense_ids = None
+    if args.raw_ids:
+        if world > 1 or args.cdc or args.fraud_reports or args.late_terminals > 0:
+            raise SystemExit("--raw-ids runs at world 1 without --cdc, --fraud-reports and --late-terminals")
+        dense_ids = {k: d[k] for k in ("customer", "terminal")}
+        for k in dense_ids:
+            d[k] = raw_id_scramble(d[k], *RAW_ID_SCRAMBLE[k])
 
     wire = None
     if args.cdc:
@@ -334,9 +363,21 @@ def main():
     else:
         sc = StreamScorer(forest, n_c, args.terminals, customer_ring=args.customer_ring,
                           terminal_ring=args.terminal_ring, max_batch=cap,
-                          terminal_lateness_days=1 if args.late_terminals > 0 else 0)
-    cols = [("ts", torch.int64), ("customer", torch.int32), ("amount", torch.float64), ("terminal", torch.int32),
+                          terminal_lateness_days=1 if args.late_terminals > 0 else 0, raw_ids=args.raw_ids)
+    id_t, id_b = (torch.int64, 8) if args.raw_ids else (torch.int32, 4)
+    row_b = 17 + 2 * id_b  # bytes per row of a packed batch
+    cols = [("ts", torch.int64), ("customer", id_t), ("amount", torch.float64), ("terminal", id_t),
             ("fraud", torch.uint8)]
+    # --raw-ids: the dense scorer the raw one is checked against, fed the original ids
+    dense = StreamScorer(forest, n_c, args.terminals, customer_ring=args.customer_ring,
+                         terminal_ring=args.terminal_ring, max_batch=cap) if args.raw_ids else None
+
+    def dense_step(a, b):
+        """the dense scorer over rows [a, b) (after run / one staged them) -> probabilities on the host"""
+        ids = [T(dense_ids[k][a:b], torch.int32) for k in ("customer", "terminal")]
+        p = dense.score(T(d["ts"][a:b], torch.int64), ids[0], T(d["amount"][a:b], torch.float64), ids[1],
+                        T(d["fraud"][a:b], torch.uint8))
+        return p.cpu().numpy().copy()
     reports = None
     if args.fraud_reports:
         if world > 1 or args.cdc:
@@ -389,12 +430,12 @@ def main():
     # (ts 8n | amount 8n | customer 4n | terminal 4n | fraud n bytes: every column aligned), as a
     # consumer would fill it -- one host-to-device copy instead of five (each copy costs ~9 us of
     # enqueue gap: 100 -> ~35 us per 64k batch, profiles/r06e trace); packed up front, untimed
-    packed_cols = [("ts", torch.int64, 8), ("amount", torch.float64, 8), ("customer", torch.int32, 4),
-                   ("terminal", torch.int32, 4), ("fraud", torch.uint8, 1)]
-    dstage = torch.empty(25 * cap, dtype=torch.uint8, device=dev)
+    packed_cols = [("ts", torch.int64, 8), ("amount", torch.float64, 8), ("customer", id_t, id_b),
+                   ("terminal", id_t, id_b), ("fraud", torch.uint8, 1)]
+    dstage = torch.empty(row_b * cap, dtype=torch.uint8, device=dev)
 
     def pack(a, b):
-        buf = torch.empty(25 * (b - a), dtype=torch.uint8).pin_memory()
+        buf = torch.empty(row_b * (b - a), dtype=torch.uint8).pin_memory()
         o = 0
         for k, _, w in packed_cols:
             buf[o:o + w * (b - a)].copy_(pin[k][a:b].view(torch.uint8))
@@ -415,8 +456,8 @@ def main():
 
     def run_packed(k, ev=None):
         buf = packed[k]
-        n = buf.numel() // 25
-        dstage[:25 * n].copy_(buf, non_blocking=True)
+        n = buf.numel() // row_b
+        dstage[:row_b * n].copy_(buf, non_blocking=True)
         if ev is not None:
             ev[0].record()
         if graph:
@@ -449,6 +490,8 @@ def main():
         if reports is not None and day_cuts[k] < day_cuts[k + 1]:
             report_due(int(day_cuts[k]))
         run(int(day_cuts[k]), int(day_cuts[k + 1]))
+        if dense is not None and day_cuts[k] < day_cuts[k + 1]:
+            dense_step(int(day_cuts[k]), int(day_cuts[k + 1]))
     sc.state.check()
     t_hist = time.perf_counter() - t_hist
 
@@ -459,7 +502,7 @@ def main():
     if wire is None and not args.column_copies:
         packed = [pack(int(bounds[k]), int(bounds[k + 1])) for k in range(n_warm + n_timed)]
         if graph:
-            for n in sorted({b.numel() // 25 for b in packed}):
+            for n in sorted({b.numel() // row_b for b in packed}):
                 sc.score_graph(*stage_views(n), out_host=out_h, replay=False)
     one = (lambda k, ev=None: run_packed(k, ev)) if packed is not None else \
         (lambda k, ev=None: run(int(bounds[k]), int(bounds[k + 1]), ev))
@@ -470,10 +513,17 @@ def main():
             run_cdc(k)
         else:
             one(k)
+        if dense is not None:
+            dense_step(int(bounds[k]), int(bounds[k + 1]))
     if world > 1:
         dist.barrier()
     lat, dev_ms, rows = [], [], 0
     rep_ms, n_rep = [], 0
+    p_dense = None
+    if dense is not None and n_timed:  # the first timed batch through the dense scorer, before the clock starts
+        p_dense = dense_step(int(bounds[n_warm]), int(bounds[n_warm + 1]))
+        dense.state.check()
+        dense = None  # its state is not needed any more
     for k in range(n_warm, n_warm + n_timed):
         if reports is not None:  # before the batch, outside its latency: device time of the report call alone
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -485,6 +535,9 @@ def main():
         rows += run_cdc(k, ev) if wire is not None else one(k, ev)
         lat.append((time.perf_counter() - t0) * 1e3)
         dev_ms.append(ev[0].elapsed_time(ev[1]))
+        if p_dense is not None and k == n_warm:
+            if not np.array_equal(out_h[:len(p_dense)].numpy(), p_dense) or rows != len(p_dense):
+                raise SystemExit("--raw-ids: the first timed batch's probabilities differ from the dense run's")
     sc.state.check()
     lat, dev_ms = np.array(lat), np.array(dev_ms)
     total_rows = rows
@@ -541,6 +594,17 @@ def main():
                                  **sc.state.late_counts(),
                                  "what": "the held customers' rows arrive one micro-batch late; value / device_p50_ms "
                                          "above are this run's (k_stream_process<W, true>)"}
+    if args.raw_ids:
+        kc = sc.key_counts()
+        out["raw_ids"] = {"raw_ids_match_dense": p_dense is not None, "key_counts": kc,
+                          "keydir_bytes": {"customers": sc.customers.memory_bytes,
+                                           "terminals": sc.terminals.memory_bytes},
+                          "what": "ids scrambled to 64-bit values (id * odd constant + offset > 2^40), mapped by the "
+                                  "two key directories inside the batch's graph; value / device_p50_ms above are "
+                                  "this run's"}
+        out["raw_ids_match_dense"] = p_dense is not None
+        if any(c["refused_full"] or c["refused_reserved"] or c["misses"] for c in kc.values()):
+            raise SystemExit(f"--raw-ids: the directories refused rows: {kc}")
     if args.snapshot:
         if world > 1:
             raise SystemExit("--snapshot runs at world 1")

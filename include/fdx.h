@@ -883,6 +883,53 @@ int fdx_stream_restore(fdx_stream s, const void *snap_d, size_t snap_bytes, int6
                        int64_t customer_step, int64_t terminal_first, int64_t terminal_step, int32_t flags,
                        void *workspace_d, size_t workspace_bytes, void *stream);
 
+/* ---- f-9: key directory -- raw 64-bit ids in front of the stream state (csrc/fdx_keydir.hip) --
+ * The stream state is addressed by dense int32 ids in [0, n).  A CDC stream brings arbitrary
+ * int64 ids and new ones in every batch (the reference's scoring job LEFT JOINs on customer_id /
+ * terminal_id, pyspark/scripts/fraud_detection.py:118-122).  A key directory is a persistent
+ * device hash table from a raw int64 key to a dense int32 id, with the reverse map key_of[id];
+ * one per key space (customers, terminals).  fdx_keydir_map turns a batch of raw ids into dense
+ * ids on the device -- no host read, no allocation -- so it can be captured in a HIP graph in
+ * front of fdx_stream_update.
+ * Numbering: a new key gets the next free id.  The new keys of one batch are numbered in the
+ *   order of their FIRST OCCURRENCE in the batch (row order), continuing from the number of keys
+ *   held: over a whole stream the ids are pandas.factorize(all keys in arrival order)[0].  They
+ *   depend neither on the thread scheduling nor on the hash, so two runs give the same ids, the
+ *   same state bytes and the same snapshots.
+ * Modes: opts = FDX_KEYDIR_INSERT finds or inserts.  opts = 0 only looks up: a key not held gives
+ *   -1, the row is counted as a miss and nothing is written to the directory.
+ * Refusals (a refused row gets ids_d[r] = -1 and is counted; none of them touches another row):
+ *   reserved   INT64_MIN is the table's empty pattern and cannot be a key.  Every other int64
+ *              is valid, -1 and INT64_MAX included.
+ *   full       with INSERT, once `capacity` ids are taken: the new keys that still fit, in
+ *              first-occurrence order, get the last ids; the rows of the others get -1.  Keys
+ *              already held keep mapping.  A refused key is not remembered: it is new again for a
+ *              larger directory (grow: fdx_keydir_keys -> create -> fdx_keydir_load).
+ *   -1 reaches fdx_stream_update / fdx_stream_report_frauds unchanged: status bit 4 (key out of
+ *   range), the row is skipped.  So a fraud report (mapped without INSERT) that names a terminal
+ *   the stream never saw raises exactly as an id out of range does.
+ * Capacity: `capacity` keys in [1, 2^30]; the table has the power of two >= 2 * capacity slots of
+ *   16 bytes, plus 8 bytes per key for key_of and 5 bytes per row of max_batch of scratch.
+ * fdx_keydir_map: n <= max_batch; n == 0 is a no-op.  keys_d and ids_d must not overlap.
+ * fdx_keydir_counts: counts_h = {keys held, rows refused: directory full, rows refused: reserved
+ *   key, lookup misses}; cumulative since create / reset (keys held: current); synchronises.
+ * fdx_keydir_keys: keys_out_d[id] = key for id < *n_h = keys held; cap < keys held:
+ *   FDX_E_INVALID, nothing written (*n_h is still set).  Synchronises.
+ * fdx_keydir_load: into an EMPTY directory, key i gets id i.  n > capacity, a directory that
+ *   holds keys, a duplicate or the reserved key: FDX_E_INVALID, the directory stays (is again)
+ *   empty.  Synchronises (a cold path: restart, growth).
+ * fdx_keydir_reset empties the directory and zeroes the counters; addresses do not move. */
+typedef struct fdx_keydir_s *fdx_keydir;
+#define FDX_KEYDIR_INSERT 1
+int fdx_keydir_create(int64_t capacity, int64_t max_batch, fdx_keydir *out, void *stream);
+int fdx_keydir_destroy(fdx_keydir d);
+int fdx_keydir_reset(fdx_keydir d, void *stream);
+int fdx_keydir_memory(fdx_keydir d, size_t *bytes);
+int fdx_keydir_map(fdx_keydir d, const int64_t *keys_d, int64_t n, int32_t opts, int32_t *ids_d, void *stream);
+int fdx_keydir_counts(fdx_keydir d, int64_t counts_h[4], void *stream);
+int fdx_keydir_keys(fdx_keydir d, int64_t *keys_out_d, int64_t cap, int64_t *n_h, void *stream);
+int fdx_keydir_load(fdx_keydir d, const int64_t *keys_d, int64_t n, void *stream);
+
 /* f-4 delay-aware split and Card-Precision@k (shared_functions.py:133-188, :352-411).
  * fdx_train_test_split: train_d[i] = t_lo <= ts_d[i] < t_hi; test_d[i] = the row is on test
  *   day d = day_d[i] - (min train day + delta_train + delta_delay), 0 <= d < delta_test, and

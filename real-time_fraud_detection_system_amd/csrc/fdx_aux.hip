@@ -123,14 +123,7 @@ __device__ __forceinline__ unsigned long long dedup_ukey(int64_t k) { return (un
 __device__ __forceinline__ unsigned long long dedup_uts(int64_t t) {  // signed -> order-preserving unsigned
     return (unsigned long long)t ^ 0x8000000000000000ull;
 }
-__device__ __forceinline__ uint32_t dedup_hash(unsigned long long k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return (uint32_t)k;
-}
+__device__ __forceinline__ uint32_t dedup_hash(unsigned long long k) { return (uint32_t)mix64(k); }
 __global__ void __launch_bounds__(256) k_dedup_init(unsigned long long *__restrict__ tkey,
                                                     unsigned long long *__restrict__ tts, int32_t *__restrict__ tpos,
                                                     int64_t cap) {

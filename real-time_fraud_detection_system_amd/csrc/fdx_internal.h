@@ -122,6 +122,17 @@ struct RollSum {
     }
 };
 
+// The 64-bit finaliser the open-addressing tables hash their keys with (the dedup table of
+// fdx_aux.hip, the key directory of fdx_keydir.hip): every input bit reaches every output bit.
+__device__ __forceinline__ unsigned long long mix64(unsigned long long k) {
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
 constexpr int64_t kNsPerSec = 1000000000LL;
 constexpr int32_t kSecPerDay = 86400, kSecPerHour = 3600;
 

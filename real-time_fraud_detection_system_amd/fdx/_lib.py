@@ -26,6 +26,7 @@ FDX_KEY_MOD, FDX_KEY_DIV, FDX_KEY_SUB = 0, 1, 2
 FDX_SELECT_LATEST, FDX_SELECT_FIRST_IN_RANGE = 0, 1  # fdx_table_select
 FDX_SNAPSHOT_HEADER_BYTES = 512
 FDX_RESTORE_COUNTERS = 1  # fdx_stream_restore's flags
+FDX_KEYDIR_INSERT = 1  # fdx_keydir_map's opts
 MAX_WINDOWS = 8
 MAX_FEATURES = 32
 
@@ -136,6 +137,14 @@ SIGNATURES = {
                                            P, c_sz, P]),
     "fdx_stream_snapshot_info": (ctypes.c_int, [P, c_sz, ctypes.POINTER(SnapshotInfo)]),
     "fdx_stream_restore": (ctypes.c_int, [P, P, c_sz, c_i64, c_i64, c_i64, c_i64, c_i32, P, c_sz, P]),
+    "fdx_keydir_create": (ctypes.c_int, [c_i64, c_i64, P, P]),
+    "fdx_keydir_destroy": (ctypes.c_int, [P]),
+    "fdx_keydir_reset": (ctypes.c_int, [P, P]),
+    "fdx_keydir_memory": (ctypes.c_int, [P, P]),
+    "fdx_keydir_map": (ctypes.c_int, [P, P, c_i64, c_i32, P, P]),
+    "fdx_keydir_counts": (ctypes.c_int, [P, P, P]),
+    "fdx_keydir_keys": (ctypes.c_int, [P, P, c_i64, P, P]),
+    "fdx_keydir_load": (ctypes.c_int, [P, P, c_i64, P]),
     "fdx_train_test_split": (ctypes.c_int, [P, P, P, P, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, P, P, P,
                                             c_sz, P, P]),
     "fdx_card_precision_workspace_size": (ctypes.c_size_t, [c_i32]),

@@ -20,6 +20,8 @@ arrive within the delay keep the stream bit-identical to the batch path over the
 
   StreamState          device state + fdx_stream_update (features of a batch) +
                        fdx_stream_report_frauds (delayed labels)
+  KeyDirectory         device hash table raw int64 id -> dense state row (fdx_keydir_*), for
+                       streams whose ids are not 0..n-1 (StreamScorer(raw_ids=True))
   StreamScorer         StreamState + the forest (scale + predict_proba) per batch
   ShardedStreamScorer  one process per GPU: customers sharded by id range, terminals owned
                        by id % world, one RCCL all-to-all there and back per batch (the
@@ -40,6 +42,7 @@ _STATUS = {1: "customer ring overflow (raise customer_ring)", 2: "terminal ring 
            16: "a late terminal row reaches past the ring (raise terminal_ring)"}
 LABEL_OUTCOMES = ("on_time", "late", "duplicate", "expired", "unmatched")  # fdx_stream_label_counts
 LATE_COUNTS = ("late_rows", "late_past_delay")  # fdx_stream_late_counts
+KEY_COUNTS = ("held", "refused_full", "refused_reserved", "misses")  # fdx_keydir_counts
 
 
 def _as_bytes_tensor(snap) -> torch.Tensor:
@@ -93,6 +96,95 @@ def load_snapshot(path) -> torch.Tensor:
     t = torch.empty(a.size, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
     t.numpy()[:] = a
     return t
+
+
+def save_keys(path, d) -> None:
+    """StreamScorer.snapshot_keys()'s dict to a file: an .npz of plain little-endian int64 arrays
+    (no pickle).  It travels beside the state snapshot (save_snapshot), whose format it leaves alone."""
+    import numpy as np
+
+    with open(path, "wb") as f:
+        np.savez(f, **{k: v.cpu().numpy().astype("<i8", copy=False) for k, v in d.items()})
+
+
+def load_keys(path) -> dict:
+    """-> {"customers": int64 tensor, "terminals": int64 tensor} on the host (restore_keys takes it)."""
+    import numpy as np
+
+    with np.load(path, allow_pickle=False) as z:
+        return {k: torch.from_numpy(z[k].astype(np.int64)) for k in z.files}
+
+
+class KeyDirectory:
+    """Raw int64 keys -> dense int32 ids on the current GPU (include/fdx.h, f-9): a new key gets
+    the next free id, new keys of a batch in the order of their first occurrence, so over a
+    stream the ids are pandas.factorize of the keys in arrival order.  INT64_MIN is reserved."""
+
+    def __init__(self, capacity: int, max_batch: int = 65536, stream=None):
+        self.device = ops.require_gpu()
+        self.capacity, self.max_batch = int(capacity), int(max_batch)
+        h = ctypes.c_void_p()
+        check(_lib.load().fdx_keydir_create(self.capacity, self.max_batch, ctypes.byref(h), ops._s(stream)),
+              "fdx_keydir_create")
+        self._h = h
+        b = ctypes.c_size_t()
+        check(_lib.load().fdx_keydir_memory(h, ctypes.byref(b)), "fdx_keydir_memory")
+        self.memory_bytes = b.value
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.fdx_keydir_destroy(h)
+            self._h = None
+
+    def reset(self, stream=None):
+        check(_lib.load().fdx_keydir_reset(self._h, ops._s(stream)), "fdx_keydir_reset")
+
+    def map(self, keys, insert: bool = True, out=None, stream=None) -> torch.Tensor:
+        """-> int32 ids of the int64 device tensor `keys` (at most max_batch rows), stream-ordered,
+        no host read.  insert: new keys get ids; else lookup only.  -1: the row was refused (the
+        directory is full, the reserved key) or, without insert, not held; counts() tells which."""
+        ops._dev(keys, torch.int64, "keys")
+        n = keys.numel()
+        if n > self.max_batch:
+            raise FdxError(f"batch of {n} keys > max_batch {self.max_batch}")
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=keys.device)
+        ops._dev(out, torch.int32, "out")
+        if out.numel() != n:
+            raise FdxError(f"out has {out.numel()} rows, keys has {n}")
+        check(_lib.load().fdx_keydir_map(self._h, ops._ptr(keys), n, _lib.FDX_KEYDIR_INSERT if insert else 0,
+                                         ops._ptr(out), ops._s(stream)), "fdx_keydir_map")
+        return out
+
+    def counts(self, stream=None) -> dict:
+        """Synchronise; -> {held, refused_full, refused_reserved, misses}: keys held now, rows
+        refused / missed since create / reset."""
+        c = (ctypes.c_int64 * len(KEY_COUNTS))()
+        check(_lib.load().fdx_keydir_counts(self._h, c, ops._s(stream)), "fdx_keydir_counts")
+        return dict(zip(KEY_COUNTS, (int(v) for v in c)))
+
+    def keys(self, stream=None) -> torch.Tensor:
+        """Synchronise; -> the keys held as a device int64 tensor, keys()[id] = key."""
+        out = torch.empty(self.counts(stream)["held"], dtype=torch.int64, device=self.device)
+        n = ctypes.c_int64()
+        check(_lib.load().fdx_keydir_keys(self._h, ops._ptr(out), out.numel(), ctypes.byref(n), ops._s(stream)),
+              "fdx_keydir_keys")
+        return out[:n.value]
+
+    def load(self, keys, stream=None):
+        """Into the EMPTY directory: keys[i] gets id i (int64 tensor, device or host).  More keys
+        than the capacity, a duplicate or the reserved key raises and the directory stays empty."""
+        k = keys.to(self.device).contiguous()
+        ops._dev(k, torch.int64, "keys")
+        check(_lib.load().fdx_keydir_load(self._h, ops._ptr(k), k.numel(), ops._s(stream)), "fdx_keydir_load")
+
+    def resized(self, capacity: int) -> "KeyDirectory":
+        """-> a new directory of `capacity` keys holding this one's keys under the same ids (a
+        cold path; keys this one refused are new to it)."""
+        d = KeyDirectory(capacity, self.max_batch)
+        d.load(self.keys())
+        return d
 
 
 class StreamState:
@@ -309,8 +401,14 @@ class StreamScorer:
 
     def __init__(self, forest: ops.Forest, n_customers: int, n_terminals: int, windows_days=(1, 7, 30),
                  delay_days=7, customer_ring=256, terminal_ring=256, max_batch=65536,
-                 flags_mode=_lib.FDX_FLAGS_NOTEBOOK, fused=True, terminal_lateness_days=0):
+                 flags_mode=_lib.FDX_FLAGS_NOTEBOOK, fused=True, terminal_lateness_days=0, raw_ids=False):
+        """raw_ids: customer / terminal are raw int64 ids (any value but INT64_MIN, new ones in
+        any batch) in score, score_graph, report_frauds and score_cdc; two KeyDirectory of
+        capacities n_customers / n_terminals number them on the device, inside the batch (and
+        inside score_graph's graph).  A key beyond a capacity raises like an id out of range:
+        grow() before that.  False: dense int32 ids in [0, n), no directory, nothing added."""
         self.forest = forest
+        self.raw_ids = bool(raw_ids)
         self.state = StreamState(n_customers, n_terminals, windows_days, delay_days, customer_ring, terminal_ring,
                                  max_batch, flags_mode, terminal_lateness_days=terminal_lateness_days)
         W = self.state.W
@@ -327,6 +425,66 @@ class StreamScorer:
             self.X = torch.empty((max_batch, 3 + 4 * W), dtype=torch.float64, device=dev)
         self.ws = ops.workspace(forest.workspace_size_max(max_batch), dev)
         self.proba = torch.empty(max_batch, dtype=torch.float64, device=dev)
+        if self.raw_ids:  # per-scorer id buffers, max_batch long: score_graph's key does not change
+            self.customers, self.terminals = KeyDirectory(n_customers, max_batch), KeyDirectory(n_terminals, max_batch)
+            self._cid = torch.empty(max_batch, dtype=torch.int32, device=dev)
+            self._tid = torch.empty(max_batch, dtype=torch.int32, device=dev)
+
+    def _dense(self, customer, terminal):
+        """raw_ids: the batch's raw int64 ids -> dense ids (new keys inserted), on the stream."""
+        if not self.raw_ids:
+            return customer, terminal
+        n = customer.numel()
+        if n > self.state.max_batch:
+            raise FdxError(f"batch of {n} rows > max_batch {self.state.max_batch}")
+        return (self.customers.map(customer, True, self._cid[:n]), self.terminals.map(terminal, True, self._tid[:n]))
+
+    def key_counts(self) -> dict:
+        """raw_ids: synchronise; -> {"customers": KeyDirectory.counts(), "terminals": ...}."""
+        self._need_raw("key_counts")
+        return {"customers": self.customers.counts(), "terminals": self.terminals.counts()}
+
+    def _need_raw(self, what):
+        if not self.raw_ids:
+            raise FdxError(f"{what} needs a scorer made with raw_ids=True")
+
+    def snapshot_keys(self) -> dict:
+        """raw_ids: -> {"customers": int64 tensor, "terminals": int64 tensor}, tensor[id] = raw key
+        (save_keys / load_keys).  Taken with snapshot(), the pair restores the stream."""
+        self._need_raw("snapshot_keys")
+        return {"customers": self.customers.keys(), "terminals": self.terminals.keys()}
+
+    def restore_keys(self, d):
+        """raw_ids: load snapshot_keys()'s dict into the (empty) directories."""
+        self._need_raw("restore_keys")
+        self.customers.load(d["customers"])
+        self.terminals.load(d["terminals"])
+
+    def grow(self, n_customers=None, n_terminals=None):
+        """New key capacities (None: unchanged), a cold path: the window state moves through
+        snapshot -> StreamState.from_snapshot, the directories through keys -> resized.  Waits
+        for the status of the batches so far (a flagged batch raises here).  Addresses move, so
+        the graphs score_graph captured are dropped.  As after any restore, late terminal rows
+        are accepted on the restored state's terms (StreamState.restore); late_counts restart."""
+        st = self.state
+        st.poll(block=True)
+        nc = st.n_customers if n_customers is None else int(n_customers)
+        nt = st.n_terminals if n_terminals is None else int(n_terminals)
+        if nc < st.n_customers or nt < st.n_terminals:
+            raise FdxError("grow cannot shrink a key capacity")
+        new = StreamState.from_snapshot(st.snapshot(), n_customers=nc, n_terminals=nt, customer_ring=st.customer_ring,
+                                        terminal_ring=st.terminal_ring, max_batch=st.max_batch)
+        if st.terminal_lateness_ns:
+            check(_lib.load().fdx_stream_set_terminal_lateness(new._h, st.terminal_lateness_ns),
+                  "fdx_stream_set_terminal_lateness")
+            new.terminal_lateness_ns = st.terminal_lateness_ns
+        if self.raw_ids:
+            if nc != st.n_customers:
+                self.customers = self.customers.resized(nc)
+            if nt != st.n_terminals:
+                self.terminals = self.terminals.resized(nt)
+        self.state = new
+        self.__dict__.pop("_graphs", None)
 
     def _no_labels(self, n):
         """fraud = None: the batch's labels are not known yet (report_frauds brings them).  One
@@ -348,6 +506,11 @@ class StreamScorer:
         """StreamState.report_frauds on the current stream, with score()'s status polling (a
         terminal id out of range raises at the next call or finish())."""
         self.state.poll()
+        if self.raw_ids:  # lookup only: a terminal the stream never saw -> -1 -> status bit 4
+            n = terminal.numel()
+            if n > self.state.max_batch:
+                raise FdxError(f"batch of {n} reports > max_batch {self.state.max_batch}")
+            terminal = self.terminals.map(terminal, False, self._tid[:n])
         self.state.report_frauds(ts, terminal)
         self.state.watch()
 
@@ -373,6 +536,7 @@ class StreamScorer:
         n = ts.numel()
         if fraud is None:
             fraud = self._no_labels(n)
+        customer, terminal = self._dense(customer, terminal)
         if not self.fused:
             X = self.state.update(ts, customer, amount, terminal, fraud, X=self.X[:n])
             out = self.forest.predict(X, ws=self.ws, out=self.proba[:n])
@@ -428,6 +592,7 @@ class StreamScorer:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
+                customer, terminal = self._dense(customer, terminal)
                 st.update(ts, customer, amount, terminal, fraud, term_records=trec, cust_nb=cnb, cust_sum=csum)
                 ops.forest_prepare_grouped(self.forest, self.flags_mode, ts, amount, cnb, csum, None, None, trec,
                                            self.ws, n=n, val_is_sum=True)
@@ -502,7 +667,18 @@ class StreamScorer:
         m, b = int(c["host"][0]), int(c["host"][1])
         if b:
             raise FdxUnsupported("CDC batch: a tx_amount field of 0 or > 8 bytes, or tx_id -1 (reserved)")
-        out = self.score(c["ts_k"][:m], c["cust"][:m], c["amt_k"][:m], c["term"][:m], c["fr_k"][:m])
+        if not self.raw_ids:
+            out = self.score(c["ts_k"][:m], c["cust"][:m], c["amt_k"][:m], c["term"][:m], c["fr_k"][:m])
+            return out, c["rows"][:m]
+        # raw ids: the kept records' int64 ids, gathered by their batch positions (the compaction's
+        # int32 columns narrow them); only kept records reach the directories
+        if "cust64" not in c:
+            c["cust64"] = torch.empty(self.state.max_batch, dtype=torch.int64, device=dev)
+            c["term64"] = torch.empty(self.state.max_batch, dtype=torch.int64, device=dev)
+        if m:
+            for src, dst in ((customer_id, c["cust64"]), (terminal_id, c["term64"])):
+                check(L.fdx_gather(P(src), 8, P(c["rows"]), m, P(dst), S), "fdx_gather")
+        out = self.score(c["ts_k"][:m], c["cust64"][:m], c["amt_k"][:m], c["term64"][:m], c["fr_k"][:m])
         return out, c["rows"][:m]
 
 
