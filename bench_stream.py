@@ -170,6 +170,11 @@ def parse(argv=None):
                          "(raw_id_scramble) into a StreamScorer(raw_ids=True): the key directories map them "
                          "inside the batch's graph.  A dense scorer runs beside it up to the first timed "
                          "batch, whose probabilities must be bit-identical (raw_ids_match_dense)")
+    ap.add_argument("--retire", type=float, default=0.0, metavar="SHARE",
+                    help="with --raw-ids, after the streamed day: time StreamScorer.retire_idle at a watermark that "
+                         "leaves SHARE of the customers idle (0 < SHARE < 1), the state re-created from a snapshot "
+                         "for every repeat, against a device-to-device copy of the bytes the move touches")
+    ap.add_argument("--retire-repeats", type=int, default=10)
     return ap.parse_args(argv)
 
 
@@ -244,6 +249,99 @@ def measure_snapshot(state, repeats=10):
                     "copy = device-to-device copy of snapshot_bytes, alternated with the calls"}
 
 
+def measure_retire(sc, share, repeats=10):
+    """Time StreamScorer.retire_idle on the scorer's state at a watermark that leaves `share` of the
+    customers idle (the terminals' share follows from it), with HIP events around the whole call,
+    alternated with a device-to-device copy of the bytes the in-place move touches (the records
+    and rings of the keys that move); one warm-up round, then `repeats`.  A retirement mutates the
+    state, so every round first puts back the snapshot and the keys taken once.  Then three
+    rounds with events between the phases (plan, apply, the two directory rebuilds).  -> dict."""
+    import numpy as np
+    import torch
+
+    from fdx.streaming import snapshot_info
+
+    st = sc.state
+    snap, keys = sc.snapshot(), sc.snapshot_keys()
+    f = snapshot_info(snap)
+    W = st.W
+    rec = snap[f["section_offset"][0]:f["section_offset"][1]].view(torch.int64).view(-1, 2 + 6 * W)
+    last = rec[rec[:, 0] > 0, 1]
+    horizon = max(st.windows_days) * 86400 * 10 ** 9
+    watermark = int(torch.sort(last).values[int(share * (last.numel() - 1))].item()) + horizon
+
+    def put_back():
+        st.restore(snap, counters=False)
+        for d, k in ((sc.customers, "customers"), (sc.terminals, "terminals")):
+            d.reset()
+            d.load(keys[k])
+
+    cmap, tmap, counts = st.retire_plan(watermark)
+    key_bytes = ((2 + 6 * W) * 8 + st.customer_ring * 16, (4 + 2 * W) * 8 + st.terminal_ring * 8)
+    moved_keys = []
+    for m in (cmap, tmap):
+        moves = (m >= 0) & (m != torch.arange(m.numel(), dtype=torch.int32, device=m.device))
+        moved_keys.append(int(moves.sum().item()))
+    touched = moved_keys[0] * key_bytes[0] + moved_keys[1] * key_bytes[1]
+    src = torch.empty(max(touched, 1), dtype=torch.uint8, device=st.device)
+    dst = torch.empty_like(src)
+    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+    ms = {"retire": [], "copy": []}
+    result = None
+    for i in range(repeats + 1):
+        put_back()
+        e = [ev() for _ in range(4)]
+        e[0].record()
+        r = sc.retire_idle(watermark)
+        e[1].record()
+        e[2].record()
+        dst.copy_(src)
+        e[3].record()
+        torch.cuda.synchronize()
+        if result is None:
+            result = r
+        elif r != result:
+            raise SystemExit("--retire: two rounds retired different keys")
+        if i:  # round 0 warms up
+            ms["retire"].append(e[0].elapsed_time(e[1]))
+            ms["copy"].append(e[2].elapsed_time(e[3]))
+    after = bytes(sc.snapshot()[:512].cpu().numpy())
+    phases = {"plan": [], "apply": [], "remap_customers": [], "remap_terminals": []}
+    for _ in range(3):
+        put_back()
+        e = [ev() for _ in range(5)]
+        e[0].record()
+        cm, tm, c = st.retire_plan(watermark)
+        e[1].record()
+        st.retire_apply(cm, c["customers"]["kept"], tm, c["terminals"]["kept"])
+        e[2].record()
+        sc.customers.remap(cm, c["customers"]["kept"])
+        e[3].record()
+        sc.terminals.remap(tm, c["terminals"]["kept"])
+        e[4].record()
+        torch.cuda.synchronize()
+        for j, k in enumerate(phases):
+            phases[k].append(e[j].elapsed_time(e[j + 1]))
+    if bytes(sc.snapshot()[:512].cpu().numpy()) != after:
+        raise SystemExit("--retire: the phase-by-phase rounds end in another snapshot header")
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    n_keys = {"customers": int(last.numel()), "terminals": counts["terminals"]["kept"] + counts["terminals"]["retired"]}
+    return {"watermark_ns": watermark, "result": result,
+            "idle_share": {k: round(result[k]["retired"] / max(n_keys[k], 1), 4) for k in n_keys},
+            "keys_with_rows": n_keys, "moved_keys": {"customers": moved_keys[0], "terminals": moved_keys[1]},
+            "key_bytes": {"customers": key_bytes[0], "terminals": key_bytes[1]}, "touched_bytes": touched,
+            "repeats": repeats, "retire_ms": round(med["retire"], 3), "copy_ms": round(med["copy"], 3),
+            "retire_over_copy": round(med["retire"] / med["copy"], 2),
+            "retire_ms_all": [round(v, 3) for v in ms["retire"]], "copy_ms_all": [round(v, 3) for v in ms["copy"]],
+            "gb_per_s": {"retire": round(2 * touched / (med["retire"] * 1e-3) / 1e9, 1),
+                         "copy": round(2 * touched / (med["copy"] * 1e-3) / 1e9, 1)},
+            "phase_ms": {k: round(float(np.median(v)), 3) for k, v in phases.items()},
+            "unit": "ms (median HIP-event time of the whole retire_idle call, host synchronisations inside "
+                    "included); copy = device-to-device copy of touched_bytes (records + whole rings of the keys "
+                    "that move), alternated with the calls; the move itself reads and writes them twice (staged); "
+                    "phase_ms: events between plan, apply and the two fdx_keydir_remap calls, three rounds"}
+
+
 def rank_shard(args, world: int, rank: int):
     """configs[4]'s key state over the ranks: rank r owns the contiguous customer ids
     [r * n_c, (r + 1) * n_c) (n_c = customers // world) and all terminals (terminal t is owned
@@ -254,6 +352,8 @@ def rank_shard(args, world: int, rank: int):
 
 def main():
     args = parse()
+    if args.retire and (not args.raw_ids or not 0 < args.retire < 1):
+        raise SystemExit("--retire SHARE needs --raw-ids and 0 < SHARE < 1")
     from bench import load_model, rehearse_host_collectives, spawn_ranks, stdout_to_stderr
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -605,6 +705,8 @@ def main():
         out["raw_ids_match_dense"] = p_dense is not None
         if any(c["refused_full"] or c["refused_reserved"] or c["misses"] for c in kc.values()):
             raise SystemExit(f"--raw-ids: the directories refused rows: {kc}")
+    if args.retire:
+        out["retire"] = measure_retire(sc, args.retire, args.retire_repeats)
     if args.snapshot:
         if world > 1:
             raise SystemExit("--snapshot runs at world 1")

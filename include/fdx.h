@@ -930,6 +930,61 @@ int fdx_keydir_counts(fdx_keydir d, int64_t counts_h[4], void *stream);
 int fdx_keydir_keys(fdx_keydir d, int64_t *keys_out_d, int64_t cap, int64_t *n_h, void *stream);
 int fdx_keydir_load(fdx_keydir d, const int64_t *keys_d, int64_t n, void *stream);
 
+/* ---- f-10: retiring idle keys -- their ids, state rows and hash slots are reused ---------------
+ * A key keeps its id and its state for as long as the directory and the state live, and a
+ * production stream meets new keys every day.  A key that has been idle for a whole horizon is
+ * provably irrelevant and can be dropped; if it comes back it is a new key, with bit-identical
+ * features:
+ *   customer  last_ts <= t - (the longest window): at its next row (ts >= t) every window drains
+ *             and the roll-sum state is re-initialised before the add (pandas' non-overlapping
+ *             window), the branch a key without rows takes;
+ *   terminal  last_ts <= t - (delay_ns + the longest window): every boundary pointer reaches n,
+ *             every count and every fraud-count difference is 0, as for a terminal without rows.
+ * A retirement is a cold path (hourly, daily; beside snapshot and grow) in three steps, with the
+ * state and the directories independent as everywhere else and joined by an id map:
+ * fdx_stream_retire_plan(watermark_ns): the caller promises that no row fed after the call has
+ *   ts < watermark_ns, in either half, late terminal rows included.  Retired: a key with n == 0, a
+ *   customer with last_ts <= watermark_ns - max window_ns, a terminal with last_ts <=
+ *   watermark_ns - (delay_ns + max window_ns); inclusive, as the update kernels compare; the
+ *   subtraction saturates at INT64_MIN.  map_d[id] = the key's new id, or -1 when retired, for
+ *   every id in [0, capacity) of that half (NULL skips the half).  New id = rank among the
+ *   survivors, so their order is kept and the state afterwards equals that of a stream fed the same
+ *   history with the retired keys' rows deleted -- ids, records, rings, snapshot bytes; no hash
+ *   order or thread schedule enters.  counts_h = {customers kept, customers retired that had rows,
+ *   terminals kept, terminals retired that had rows}.  Writes nothing to the state; synchronises.
+ * fdx_stream_retire_apply(maps, kept counts): moves records and whole rings old id -> new id in
+ *   place, in ascending chunks staged through the workspace (a bigger workspace = bigger chunks;
+ *   the ids below the first one that moves are skipped), then clears the records and chain heads of
+ *   [kept, capacity) as fdx_stream_reset does (their rings are unreachable while n == 0).  A map
+ *   that retires nothing writes nothing.  Allocations keep their addresses and sizes: a captured
+ *   graph of updates stays valid.  Status bits, the label and late counters and the restored flag
+ *   keep their values.
+ * fdx_keydir_remap(map, n_map, kept): key_of compacted by the map, the table cleared and refilled
+ *   (key_of[i] -> id i), keys held = kept; n_map >= the keys held, entries beyond them are unused.
+ *   The refusal counters keep their values; refused keys left in the table vanish (a refused key
+ *   is not remembered).  Addresses do not move.  Synchronises.
+ * A valid map: -1 for a retired id, survivors numbered 0 .. kept-1 in increasing id order.
+ * Refusals.  plan and apply are stream-ordered after earlier updates and read the status word
+ *   first: a set bit is FDX_E_UNSUPPORTED and stays set.  Everything else -- a workspace below
+ *   fdx_stream_retire_workspace_size(s, 1) resp. fdx_keydir_remap_workspace_size(d), a malformed
+ *   map, a kept count that is not the map's, a map shorter than the keys held -- is FDX_E_INVALID
+ *   with NOTHING written: the map is checked by a device pass that completes before the write
+ *   pass starts.
+ * Fraud reports.  A report that names a retired terminal is a lookup miss (-1, status bit 4), as
+ *   one for a terminal never seen (and like the rows a snapshot dropped, f-7, it can affect no
+ *   feature: it is older than delay_ns + the longest window).  Callers that do not want the raise
+ *   drop reports with ts < watermark_ns - (delay_ns + the longest window).
+ * fdx_stream_retire_workspace_size(s, chunk_keys): for chunks of chunk_keys keys (0: the default,
+ *   8192; at most the larger capacity). */
+size_t fdx_stream_retire_workspace_size(fdx_stream s, int64_t chunk_keys);
+int fdx_stream_retire_plan(fdx_stream s, int64_t watermark_ns, int32_t *cust_map_d, int32_t *term_map_d,
+                           int64_t counts_h[4], void *workspace_d, size_t workspace_bytes, void *stream);
+int fdx_stream_retire_apply(fdx_stream s, const int32_t *cust_map_d, int64_t cust_kept, const int32_t *term_map_d,
+                            int64_t term_kept, void *workspace_d, size_t workspace_bytes, void *stream);
+size_t fdx_keydir_remap_workspace_size(fdx_keydir d);
+int fdx_keydir_remap(fdx_keydir d, const int32_t *map_d, int64_t n_map, int64_t kept, void *workspace_d,
+                     size_t workspace_bytes, void *stream);
+
 /* f-4 delay-aware split and Card-Precision@k (shared_functions.py:133-188, :352-411).
  * fdx_train_test_split: train_d[i] = t_lo <= ts_d[i] < t_hi; test_d[i] = the row is on test
  *   day d = day_d[i] - (min train day + delta_train + delta_delay), 0 <= d < delta_test, and

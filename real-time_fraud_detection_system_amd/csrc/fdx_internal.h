@@ -210,6 +210,19 @@ inline unsigned stream_grid(int64_t n, int block, int64_t cap = 256 * 8) {
     return (unsigned)g;
 }
 
+// f-10: the device check of a retirement id map (fdx_stream.hip; fdx_stream_retire_apply and
+// fdx_keydir_remap run this one copy).  A valid map over n ids is -1 for a retired id and, for
+// the survivors, their rank among the survivors: 0 .. kept-1 in increasing id order.  Enqueues
+// three phases on st (flags, exclusive scan, check) and reads nothing back; afterwards, on the
+// device, res_d->bad != 0: malformed; kept: the survivors; first: the first id with map[id] != id
+// (n when there is none), so ids below it stay where they are.  flag_d: n + 1 words; scan_ws_d:
+// fdx_exclusive_scan_u32_workspace_size(n + 1) bytes.
+struct MapRes {
+    unsigned long long kept, first;
+    uint32_t bad, pad;
+};
+int map_validate(const int32_t *map_d, int64_t n, MapRes *res_d, uint32_t *flag_d, void *scan_ws_d, hipStream_t st);
+
 // The stable 64-bit LSD radix sort of fdx_rekey.hip (the one behind fdx_argsort_i64), for the
 // other translation units: ascending over all 64 bits of keys_d, n in [1, INT32_MAX).
 // *sorted_d = the sorted keys and *vals_d = per sorted position the input row index with

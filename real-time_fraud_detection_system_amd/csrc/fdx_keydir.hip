@@ -216,6 +216,25 @@ __global__ void __launch_bounds__(kBlock) k_keydir_load(const int64_t *__restric
     *err = 1;  // (n <= capacity <= slots / 2: the probe cannot run out of slots)
 }
 
+// remap (f-10), phase 1: the surviving keys in their new order, staged outside key_of (new id <=
+// old id, so a compaction in place would overwrite keys other lanes still have to read)
+__global__ void __launch_bounds__(kBlock) k_keydir_compact(const int64_t *__restrict__ key_of,
+                                                           const int32_t *__restrict__ map, int64_t held,
+                                                           int64_t *__restrict__ staged) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= held) return;
+    const int32_t to = map[i];  // validated: -1 or the rank among the survivors
+    if (to >= 0) staged[to] = key_of[i];
+}
+
+// remap, last phase: the held count (read by the next find) and the pending count
+__global__ void __launch_bounds__(kWave) k_keydir_set_held(unsigned long long *__restrict__ cnt, int64_t kept) {
+    if (threadIdx.x == 0) {
+        cnt[kHeld] = (unsigned long long)kept;
+        cnt[kPending] = 0;
+    }
+}
+
 }  // namespace
 }  // namespace fdx
 
@@ -378,5 +397,90 @@ extern "C" int fdx_keydir_load(fdx_keydir d, const int64_t *keys_d, int64_t n, v
     const unsigned long long held_new = (unsigned long long)n;
     FDX_HIP(hipMemcpyAsync(d->cnt_d, &held_new, 8, hipMemcpyHostToDevice, st));
     FDX_HIP(hipStreamSynchronize(st));  // held_new lives on this frame
+    return FDX_OK;
+}
+
+// ---- f-10: the directory after a retirement.  key_of is compacted by the id map (through the
+// workspace), the table is cleared and refilled from it (key_of[i] -> id i, as fdx_keydir_load), so
+// the retired keys' ids and slots -- and refused keys left in the table -- are free again.
+namespace {
+struct RemapWs {
+    MapRes *res;
+    uint32_t *flag;
+    void *scan;
+    int64_t *staged;
+    size_t total;
+};
+
+RemapWs remap_ws(fdx_keydir d, void *ws) {
+    char *p = reinterpret_cast<char *>(ws);
+    RemapWs w{};
+    const size_t o_flag = 256, o_scan = o_flag + al256((size_t)(d->cap + 1) * 4);
+    const size_t o_staged = o_scan + al256(fdx_exclusive_scan_u32_workspace_size(d->cap + 1));
+    w.total = o_staged + al256((size_t)d->cap * 8);
+    if (!p) return w;  // the size query
+    w.res = reinterpret_cast<MapRes *>(p);
+    w.flag = reinterpret_cast<uint32_t *>(p + o_flag);
+    w.scan = p + o_scan;
+    w.staged = reinterpret_cast<int64_t *>(p + o_staged);
+    return w;
+}
+}  // namespace
+
+extern "C" size_t fdx_keydir_remap_workspace_size(fdx_keydir d) { return d ? remap_ws(d, nullptr).total : 0; }
+
+extern "C" int fdx_keydir_remap(fdx_keydir d, const int32_t *map_d, int64_t n_map, int64_t kept, void *workspace_d,
+                                size_t workspace_bytes, void *stream) {
+    FDX_REQUIRE(d, "null key directory");
+    FDX_REQUIRE(workspace_d && workspace_bytes >= fdx_keydir_remap_workspace_size(d), "workspace too small");
+    FDX_REQUIRE(n_map >= 0 && n_map <= d->cap && (map_d || n_map == 0), "the map has %lld entries, the capacity is %lld",
+                (long long)n_map, (long long)d->cap);
+    hipStream_t st = as_stream(stream);
+    int64_t held = 0;
+    FDX_HIP(hipMemcpyAsync(&held, d->cnt_d, 8, hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    FDX_REQUIRE(n_map >= held, "the map has %lld entries, the directory holds %lld keys", (long long)n_map,
+                (long long)held);
+    FDX_REQUIRE(kept >= 0 && kept <= held, "kept %lld outside [0, %lld keys held]", (long long)kept, (long long)held);
+    const RemapWs w = remap_ws(d, workspace_d);
+    // pass 1, to completion before anything is written: the map over the ids held (entries beyond are unused)
+    int rc = map_validate(map_d, held, w.res, w.flag, w.scan, st);
+    if (rc) return rc;
+    MapRes r;
+    FDX_HIP(hipMemcpyAsync(&r, w.res, sizeof(r), hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    FDX_REQUIRE(!r.bad, "the map is malformed: -1 or the rank among the survivors, in id order");
+    FDX_REQUIRE((int64_t)r.kept == kept, "the map keeps %lld of the keys held, the call says %lld", (long long)r.kept,
+                (long long)kept);
+    // pass 2
+    if (held) {
+        hipLaunchKernelGGL(k_keydir_compact, dim3((unsigned)ceil_div(held, kBlock)), dim3(kBlock), 0, st, d->key_of_d,
+                           map_d, held, w.staged);
+        FDX_LAUNCHED("k_keydir_compact");
+    }
+    hipLaunchKernelGGL(k_keydir_clear, dim3(stream_grid(d->n_slots, kBlock)), dim3(kBlock), 0, st, d->slots_d,
+                       d->n_slots);
+    FDX_LAUNCHED("k_keydir_clear");
+    int32_t *err_d = reinterpret_cast<int32_t *>(d->cnt_d + kCounters);
+    FDX_HIP(hipMemsetAsync(err_d, 0, 4, st));
+    if (kept) {
+        hipLaunchKernelGGL(k_keydir_load, dim3((unsigned)ceil_div(kept, kBlock)), dim3(kBlock), 0, st, w.staged, kept,
+                           d->slots_d, (uint32_t)(d->n_slots - 1), d->key_of_d, err_d);
+        FDX_LAUNCHED("k_keydir_load");
+    }
+    hipLaunchKernelGGL(k_keydir_set_held, dim3(1), dim3(kWave), 0, st, d->cnt_d, kept);
+    FDX_LAUNCHED("k_keydir_set_held");
+    int32_t err = 0;
+    FDX_HIP(hipMemcpyAsync(&err, err_d, 4, hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    if (err) {  // cannot happen with a consistent directory; its keys are gone if it does
+        hipLaunchKernelGGL(k_keydir_clear, dim3(stream_grid(d->n_slots, kBlock)), dim3(kBlock), 0, st, d->slots_d,
+                           d->n_slots);
+        FDX_LAUNCHED("k_keydir_clear");
+        hipLaunchKernelGGL(k_keydir_set_held, dim3(1), dim3(kWave), 0, st, d->cnt_d, (int64_t)0);
+        FDX_LAUNCHED("k_keydir_set_held");
+        FDX_HIP(hipMemsetAsync(err_d, 0, 4, st));
+        FDX_REQUIRE(false, "remap: the directory held a duplicate or the reserved key; it is empty now");
+    }
     return FDX_OK;
 }

@@ -1220,3 +1220,303 @@ extern "C" int fdx_stream_restore(fdx_stream s, const void *snap_d, size_t snap_
     }
     return FDX_OK;
 }
+
+
+// ---------------------------------------------------------------- retiring idle keys (f-10)
+// A key whose last row lies a whole horizon (customers: the longest window; terminals: delay +
+// the longest window) before every row still to come behaves exactly like a key never seen: the
+// customer's windows all drain and RollSum::reset runs before the add, the terminal's pointers
+// all reach n and every count difference is 0.  Such keys are dropped, the survivors renumbered
+// by their rank (order kept), and the freed ids go back to the key directory (fdx_keydir_remap).
+//
+//   k_retire_mark     plan: one thread per key reads {n, last_ts} (one 16-byte load): alive flag
+//                     -> u32 array, retired keys with rows counted; then the exclusive scan
+//   k_retire_map      plan: map[id] = alive ? rank : -1; the survivor count
+//   k_map_flag/check  apply (and fdx_keydir_remap): a caller's map is checked on the device --
+//                     flags, scan, map[id] == -1 or == its rank -- before anything is written
+//   k_retire_gather   apply: the records and whole rings of one chunk of ids -> workspace
+//   k_retire_scatter  apply: workspace -> the new ids.  new(id) <= id and the map is monotone, so
+//                     a chunk's destinations never lie above its own sources, but they may
+//                     overlap sources of the SAME chunk: hence the staging, and chunk c's scatter
+//                     is a launch before chunk c + 1's gather.  The ids below the first one that
+//                     moves are skipped.
+// Rings travel whole and verbatim: positions are r & mask of the absolute n, so the unchanged
+// record with the unchanged ring is exact.  16 lanes per key on consecutive words / entries, as
+// k_snap_pack.  Nothing a launch reads by plain loads was written in that launch; no LDS but the
+// block scan that sums k_retire_mark's count.  Records and heads of [kept, capacity) are cleared
+// as fdx_stream_reset clears them; their rings are unreachable while n == 0.
+namespace fdx {
+namespace {
+
+constexpr int64_t kRetireChunk = 8192;  // keys staged per gather / scatter pair by default
+constexpr int kMoveShift = 4;           // 16 lanes per key
+
+struct RetRes {
+    MapRes map[2];
+    unsigned long long retired[2];  // plan: keys with n >= 1 that are retired
+};
+static_assert(sizeof(RetRes) <= 256, "the workspace's first 256 bytes");
+
+__global__ void __launch_bounds__(256) k_retire_mark(const int64_t *__restrict__ state, int32_t R, int64_t n_keys,
+                                                     int64_t cut, uint32_t *__restrict__ flag,
+                                                     RetRes *__restrict__ res, int32_t half) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t alive = 0, dead = 0;
+    if (i < n_keys) {
+        const longlong2 w = *reinterpret_cast<const longlong2 *>(state + i * R);  // {n, last_ts}
+        alive = w.x > 0 && w.y > cut;
+        dead = w.x > 0 && !alive;
+    }
+    if (i <= n_keys) flag[i] = alive;  // flag[n_keys] = 0 closes the scan
+    // one atomic per block: with one per wave the same-address atomics were the launch's time
+    uint32_t tot;
+    block_excl_scan<256 / kWave>(dead, &tot);
+    if (threadIdx.x == 0 && tot) atomicAdd(&res->retired[half], (unsigned long long)tot);
+}
+
+__global__ void __launch_bounds__(256) k_retire_map(const uint32_t *__restrict__ rank, int64_t n_keys,
+                                                    int32_t *__restrict__ map, RetRes *__restrict__ res,
+                                                    int32_t half) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_keys) {
+        const uint32_t r = rank[i];
+        map[i] = rank[i + 1] != r ? (int32_t)r : -1;
+    }
+    if (i == 0) res->map[half].kept = rank[n_keys];
+}
+
+__global__ void __launch_bounds__(256) k_map_flag(const int32_t *__restrict__ map, int64_t n,
+                                                  uint32_t *__restrict__ flag, MapRes *__restrict__ res) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= n) flag[i] = i < n && map[i] >= 0;
+    if (i == 0) *res = MapRes{0, (unsigned long long)n, 0, 0};
+}
+
+__global__ void __launch_bounds__(256) k_map_check(const int32_t *__restrict__ map, int64_t n,
+                                                   const uint32_t *__restrict__ rank, MapRes *__restrict__ res) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int32_t v = map[i];
+        if (v < 0 ? v != -1 : (uint32_t)v != rank[i]) atomicOr(&res->bad, 1u);
+        // In a valid map every id from the first one that moves on differs from its entry (a
+        // survivor's rank is below its id), so exactly one id differs while its predecessor does
+        // not: a plain store by that thread, where an atomicMin by every moved id took 270 us per
+        // launch over 2M ids.  (A malformed map may store several times: it is refused anyway.)
+        if ((int64_t)v != i && (i == 0 || (int64_t)map[i - 1] == i - 1)) res->first = (unsigned long long)i;
+    }
+    if (i == 0) res->kept = rank[n];  // (no other thread of this launch touches the word)
+}
+
+template <class E>
+__global__ void __launch_bounds__(256) k_retire_gather(const int64_t *__restrict__ state, const E *__restrict__ rings,
+                                                       int32_t R, int64_t ring, const int32_t *__restrict__ map,
+                                                       int64_t id0, int64_t m, int64_t *__restrict__ st_rec,
+                                                       E *__restrict__ st_ent) {
+    const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> kMoveShift;
+    if (g >= m) return;  // the whole group or none of it
+    constexpr int32_t G = 1 << kMoveShift;
+    const int32_t lane = (int32_t)threadIdx.x & (G - 1);
+    const int64_t id = id0 + g;
+    if (map[id] < 0) return;
+    for (int32_t i = lane; i < R; i += G) st_rec[g * R + i] = state[id * R + i];
+    const E *src = rings + id * ring;
+    E *dst = st_ent + g * ring;
+#pragma unroll 4
+    for (int64_t i = lane; i < ring; i += G) dst[i] = src[i];
+}
+
+template <class E>
+__global__ void __launch_bounds__(256) k_retire_scatter(const int64_t *__restrict__ st_rec, const E *__restrict__ st_ent,
+                                                        int32_t R, int64_t ring, const int32_t *__restrict__ map,
+                                                        int64_t id0, int64_t m, int64_t *__restrict__ state,
+                                                        E *__restrict__ rings) {
+    const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> kMoveShift;
+    if (g >= m) return;
+    constexpr int32_t G = 1 << kMoveShift;
+    const int32_t lane = (int32_t)threadIdx.x & (G - 1);
+    const int64_t to = map[id0 + g];  // validated: -1 or a rank <= id0 + g
+    if (to < 0) return;
+    for (int32_t i = lane; i < R; i += G) state[to * R + i] = st_rec[g * R + i];
+    const E *src = st_ent + g * ring;
+    E *dst = rings + to * ring;
+#pragma unroll 4
+    for (int64_t i = lane; i < ring; i += G) dst[i] = src[i];
+}
+
+size_t half_key_bytes(const Half &h, size_t ent_bytes) { return (size_t)h.R * 8 + (size_t)h.ring_len * ent_bytes; }
+
+struct RetWs {
+    RetRes *res;
+    uint32_t *flag;
+    void *scan;
+    char *stage;
+    size_t fixed;  // bytes before the staging area
+};
+
+RetWs ret_ws(fdx_stream s, void *ws) {
+    const int64_t m = (s->n_cust > s->n_term ? s->n_cust : s->n_term) + 1;
+    char *p = reinterpret_cast<char *>(ws);
+    RetWs w{};
+    const size_t o_flag = 256, o_scan = o_flag + al256((size_t)m * 4);
+    w.fixed = o_scan + al256(fdx_exclusive_scan_u32_workspace_size(m));
+    w.res = reinterpret_cast<RetRes *>(p);
+    if (!p) return w;  // the size query: only `fixed`
+    w.flag = reinterpret_cast<uint32_t *>(p + o_flag);
+    w.scan = p + o_scan;
+    w.stage = p + w.fixed;
+    return w;
+}
+
+size_t max_key_bytes(fdx_stream s) {
+    const size_t c = s->n_cust ? half_key_bytes(cust_half(s), sizeof(CEnt)) : 0;
+    const size_t t = s->n_term ? half_key_bytes(term_half(s), 8) : 0;
+    return c > t ? c : t;
+}
+
+// t - h without signed overflow (h >= 0): saturates at INT64_MIN, where `last_ts <= cut` holds
+// for no timestamp but INT64_MIN itself
+int64_t sat_sub(int64_t t, int64_t h) { return t < INT64_MIN + h ? INT64_MIN : t - h; }
+
+// the status word, read first (as the snapshot does): a set bit refuses and stays set
+int retire_status(fdx_stream s, hipStream_t st) {
+    int32_t flags = 0;
+    FDX_HIP(hipMemcpyAsync(&flags, s->status_d, 4, hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    if (flags) {
+        set_error("the stream state carries status bits %d (fdx_stream_status): nothing retired", flags);
+        return FDX_E_UNSUPPORTED;
+    }
+    return FDX_OK;
+}
+
+template <class E>
+int retire_move(const Half &h, E *rings, const int32_t *map_d, int64_t first, int64_t kept, int32_t *head_d,
+                char *stage, int64_t chunk, hipStream_t st) {
+    int64_t *st_rec = reinterpret_cast<int64_t *>(stage);
+    E *st_ent = reinterpret_cast<E *>(stage + (size_t)chunk * h.R * 8);  // R is even: 16-byte aligned
+    for (int64_t id0 = first; id0 < h.n_keys; id0 += chunk) {
+        const int64_t m = h.n_keys - id0 < chunk ? h.n_keys - id0 : chunk;
+        const dim3 grid((unsigned)ceil_div(m << kMoveShift, 256));
+        hipLaunchKernelGGL(k_retire_gather<E>, grid, dim3(256), 0, st, h.state, rings, h.R, (int64_t)h.ring_len,
+                           map_d, id0, m, st_rec, st_ent);
+        FDX_LAUNCHED("k_retire_gather");
+        hipLaunchKernelGGL(k_retire_scatter<E>, grid, dim3(256), 0, st, st_rec, st_ent, h.R, (int64_t)h.ring_len,
+                           map_d, id0, m, h.state, rings);
+        FDX_LAUNCHED("k_retire_scatter");
+    }
+    if (kept < h.n_keys) {
+        FDX_HIP(hipMemsetAsync(h.state + kept * h.R, 0, (size_t)(h.n_keys - kept) * h.R * 8, st));
+        FDX_HIP(hipMemsetAsync(head_d + kept, 0xFF, (size_t)(h.n_keys - kept) * 4, st));
+    }
+    return FDX_OK;
+}
+
+}  // namespace
+
+int map_validate(const int32_t *map_d, int64_t n, MapRes *res_d, uint32_t *flag_d, void *scan_ws_d, hipStream_t st) {
+    const dim3 grid((unsigned)ceil_div(n + 1, 256));
+    hipLaunchKernelGGL(k_map_flag, grid, dim3(256), 0, st, map_d, n, flag_d, res_d);
+    FDX_LAUNCHED("k_map_flag");
+    const int rc = fdx_exclusive_scan_u32(flag_d, n + 1, scan_ws_d, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_map_check, grid, dim3(256), 0, st, map_d, n, flag_d, res_d);
+    FDX_LAUNCHED("k_map_check");
+    return FDX_OK;
+}
+
+}  // namespace fdx
+
+extern "C" size_t fdx_stream_retire_workspace_size(fdx_stream s, int64_t chunk_keys) {
+    if (!s) return 0;
+    const int64_t m = s->n_cust > s->n_term ? s->n_cust : s->n_term;
+    int64_t chunk = chunk_keys > 0 ? chunk_keys : kRetireChunk;
+    if (chunk > m) chunk = m;
+    if (chunk < 1) chunk = 1;
+    return ret_ws(s, nullptr).fixed + al256((size_t)chunk * max_key_bytes(s));
+}
+
+extern "C" int fdx_stream_retire_plan(fdx_stream s, int64_t watermark_ns, int32_t *cust_map_d, int32_t *term_map_d,
+                                      int64_t counts_h[4], void *workspace_d, size_t workspace_bytes, void *stream) {
+    FDX_REQUIRE(s && counts_h, "null pointer");
+    FDX_REQUIRE(workspace_d && workspace_bytes >= fdx_stream_retire_workspace_size(s, 1), "workspace too small");
+    hipStream_t st = as_stream(stream);
+    int rc;
+    if ((rc = retire_status(s, st))) return rc;
+    const RetWs w = ret_ws(s, workspace_d);
+    FDX_HIP(hipMemsetAsync(w.res, 0, sizeof(RetRes), st));
+    const Half h[2] = {cust_half(s), term_half(s)};
+    int32_t *map[2] = {cust_map_d, term_map_d};
+    int64_t cmax = 0;
+    for (int i = 0; i < s->W; ++i) cmax = s->sw.win[i] > cmax ? s->sw.win[i] : cmax;
+    // delay + the longest window, saturating (both are >= 0)
+    const int64_t tmax = cmax > INT64_MAX - s->sw.tb[0] ? INT64_MAX : s->sw.tb[0] + cmax;
+    const int64_t cut[2] = {sat_sub(watermark_ns, cmax), sat_sub(watermark_ns, tmax)};
+    for (int i = 0; i < 2; ++i) {
+        if (!map[i] || !h[i].n_keys) continue;
+        const dim3 grid((unsigned)ceil_div(h[i].n_keys + 1, 256));
+        hipLaunchKernelGGL(k_retire_mark, grid, dim3(256), 0, st, h[i].state, h[i].R, h[i].n_keys, cut[i], w.flag,
+                           w.res, i);
+        FDX_LAUNCHED("k_retire_mark");
+        if ((rc = fdx_exclusive_scan_u32(w.flag, h[i].n_keys + 1, w.scan, st))) return rc;
+        hipLaunchKernelGGL(k_retire_map, grid, dim3(256), 0, st, w.flag, h[i].n_keys, map[i], w.res, i);
+        FDX_LAUNCHED("k_retire_map");
+    }
+    RetRes r;
+    FDX_HIP(hipMemcpyAsync(&r, w.res, sizeof(r), hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < 2; ++i) {
+        counts_h[2 * i] = (int64_t)r.map[i].kept;
+        counts_h[2 * i + 1] = (int64_t)r.retired[i];
+    }
+    return FDX_OK;
+}
+
+extern "C" int fdx_stream_retire_apply(fdx_stream s, const int32_t *cust_map_d, int64_t cust_kept,
+                                       const int32_t *term_map_d, int64_t term_kept, void *workspace_d,
+                                       size_t workspace_bytes, void *stream) {
+    FDX_REQUIRE(s, "null stream state");
+    FDX_REQUIRE(workspace_d && workspace_bytes >= fdx_stream_retire_workspace_size(s, 1), "workspace too small");
+    const Half h[2] = {cust_half(s), term_half(s)};
+    const int32_t *map[2] = {cust_map_d, term_map_d};
+    const int64_t kept[2] = {cust_kept, term_kept};
+    const char *name[2] = {"customer", "terminal"};
+    for (int i = 0; i < 2; ++i) {
+        if (!map[i]) continue;
+        FDX_REQUIRE(h[i].n_keys > 0, "a %s map for a state without a %s half", name[i], name[i]);
+        FDX_REQUIRE(kept[i] >= 0 && kept[i] <= h[i].n_keys, "%s kept %lld outside [0, %lld]", name[i],
+                    (long long)kept[i], (long long)h[i].n_keys);
+    }
+    hipStream_t st = as_stream(stream);
+    int rc;
+    if ((rc = retire_status(s, st))) return rc;
+    const RetWs w = ret_ws(s, workspace_d);
+    // pass 1, to completion before anything is written
+    for (int i = 0; i < 2; ++i)
+        if (map[i] && (rc = map_validate(map[i], h[i].n_keys, &w.res->map[i], w.flag, w.scan, st))) return rc;
+    RetRes r;
+    FDX_HIP(hipMemcpyAsync(&r, w.res, sizeof(r), hipMemcpyDeviceToHost, st));
+    FDX_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < 2; ++i) {
+        if (!map[i]) continue;
+        FDX_REQUIRE(!r.map[i].bad, "the %s map is malformed: -1 or the rank among the survivors, in id order", name[i]);
+        FDX_REQUIRE((int64_t)r.map[i].kept == kept[i], "the %s map keeps %lld keys, the call says %lld", name[i],
+                    (long long)r.map[i].kept, (long long)kept[i]);
+    }
+    // pass 2
+    const size_t avail = workspace_bytes - w.fixed;
+    if (map[0]) {
+        int64_t chunk = (int64_t)(avail / half_key_bytes(h[0], sizeof(CEnt)));
+        chunk = chunk > h[0].n_keys ? h[0].n_keys : chunk;
+        if ((rc = retire_move<CEnt>(h[0], s->cring_d, map[0], (int64_t)r.map[0].first, kept[0], s->chead_d, w.stage,
+                                    chunk, st)))
+            return rc;
+    }
+    if (map[1]) {
+        int64_t chunk = (int64_t)(avail / half_key_bytes(h[1], 8));
+        chunk = chunk > h[1].n_keys ? h[1].n_keys : chunk;
+        if ((rc = retire_move<int64_t>(h[1], s->tring_d, map[1], (int64_t)r.map[1].first, kept[1], s->thead_d,
+                                       w.stage, chunk, st)))
+            return rc;
+    }
+    return FDX_OK;
+}

@@ -145,6 +145,11 @@ SIGNATURES = {
     "fdx_keydir_counts": (ctypes.c_int, [P, P, P]),
     "fdx_keydir_keys": (ctypes.c_int, [P, P, c_i64, P, P]),
     "fdx_keydir_load": (ctypes.c_int, [P, P, c_i64, P]),
+    "fdx_stream_retire_workspace_size": (c_sz, [P, c_i64]),
+    "fdx_stream_retire_plan": (ctypes.c_int, [P, c_i64, P, P, P, P, c_sz, P]),
+    "fdx_stream_retire_apply": (ctypes.c_int, [P, P, c_i64, P, c_i64, P, c_sz, P]),
+    "fdx_keydir_remap_workspace_size": (c_sz, [P]),
+    "fdx_keydir_remap": (ctypes.c_int, [P, P, c_i64, c_i64, P, c_sz, P]),
     "fdx_train_test_split": (ctypes.c_int, [P, P, P, P, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, P, P, P,
                                             c_sz, P, P]),
     "fdx_card_precision_workspace_size": (ctypes.c_size_t, [c_i32]),

@@ -21,7 +21,9 @@ arrive within the delay keep the stream bit-identical to the batch path over the
   StreamState          device state + fdx_stream_update (features of a batch) +
                        fdx_stream_report_frauds (delayed labels)
   KeyDirectory         device hash table raw int64 id -> dense state row (fdx_keydir_*), for
-                       streams whose ids are not 0..n-1 (StreamScorer(raw_ids=True))
+                       streams whose ids are not 0..n-1 (StreamScorer(raw_ids=True));
+                       StreamScorer.retire_idle drops the keys idle for a whole horizon, so
+                       their ids and state rows are reused (fdx_stream_retire_*, fdx_keydir_remap)
   StreamScorer         StreamState + the forest (scale + predict_proba) per batch
   ShardedStreamScorer  one process per GPU: customers sharded by id range, terminals owned
                        by id % world, one RCCL all-to-all there and back per batch (the
@@ -178,6 +180,21 @@ class KeyDirectory:
         k = keys.to(self.device).contiguous()
         ops._dev(k, torch.int64, "keys")
         check(_lib.load().fdx_keydir_load(self._h, ops._ptr(k), k.numel(), ops._s(stream)), "fdx_keydir_load")
+
+    def remap(self, id_map, kept: int, stream=None):
+        """After a retirement (f-10): id_map[id] = the key's new id or -1 (int32 device tensor over
+        at least the keys held; StreamState.retire_plan makes it), kept = the survivors.  key_of
+        is compacted, the table cleared and refilled, so the retired keys' ids and slots -- and
+        refused keys left in the table -- are free again; the refusal counters keep their values.
+        A malformed map or a wrong kept raises with nothing written.  Addresses do not move.
+        Synchronises (a cold path)."""
+        ops._dev(id_map, torch.int32, "id_map")
+        L = _lib.load()
+        ws = getattr(self, "_remap_ws", None)
+        if ws is None:
+            ws = self._remap_ws = ops.workspace(L.fdx_keydir_remap_workspace_size(self._h), self.device)
+        check(L.fdx_keydir_remap(self._h, ops._ptr(id_map), id_map.numel(), int(kept), ops._ptr(ws), ws.numel(),
+                                 ops._s(stream)), "fdx_keydir_remap")
 
     def resized(self, capacity: int) -> "KeyDirectory":
         """-> a new directory of `capacity` keys holding this one's keys under the same ids (a
@@ -365,6 +382,49 @@ class StreamState:
         st.restore(snap)
         return st
 
+    def _retire_ws(self, chunk_keys=0):
+        cache = self.__dict__.setdefault("_retire_wss", {})
+        ws = cache.get(int(chunk_keys))
+        if ws is None:
+            nb = _lib.load().fdx_stream_retire_workspace_size(self._h, int(chunk_keys))
+            ws = cache[int(chunk_keys)] = ops.workspace(nb, self.device)
+        return ws
+
+    def retire_plan(self, watermark_ns: int, stream=None):
+        """Which keys can no longer influence a feature, given that no later row has
+        ts < watermark_ns (include/fdx.h, f-10): -> (cust_map, term_map, counts).  A map is an
+        int32 device tensor over the half's capacity, map[id] = the new id (the rank among the
+        survivors) or -1 when retired; None for a half the state lacks.  counts = {"customers":
+        {"kept", "retired"}, "terminals": {...}}, retired counting the keys that had rows.  Writes
+        nothing to the state; synchronises; a state with a status bit up raises FdxUnsupported."""
+        maps = [torch.empty(n, dtype=torch.int32, device=self.device) if n else None
+                for n in (self.n_customers, self.n_terminals)]
+        c = (ctypes.c_int64 * 4)()
+        ws = self._retire_ws()
+        check(_lib.load().fdx_stream_retire_plan(self._h, int(watermark_ns), ops._ptr(maps[0]), ops._ptr(maps[1]), c,
+                                                 ops._ptr(ws), ws.numel(), ops._s(stream)), "fdx_stream_retire_plan")
+        counts = {"customers": {"kept": int(c[0]), "retired": int(c[1])},
+                  "terminals": {"kept": int(c[2]), "retired": int(c[3])}}
+        return maps[0], maps[1], counts
+
+    def retire_apply(self, cust_map, cust_kept, term_map, term_kept, chunk_keys=0, stream=None):
+        """Move the surviving keys' records and rings to their new ids, in place, and clear the
+        records of the ids from kept on (a map of None skips that half).  chunk_keys: keys staged
+        per gather / scatter pair (0: the default).  A malformed map, a wrong kept or a status bit
+        up raises with nothing written.  State addresses do not move: a captured score_graph
+        stays valid."""
+        for m, name in ((cust_map, "cust_map"), (term_map, "term_map")):
+            if m is not None:
+                ops._dev(m, torch.int32, name)
+        if cust_map is not None and cust_map.numel() != self.n_customers:
+            raise FdxError(f"cust_map has {cust_map.numel()} entries, the state {self.n_customers} customers")
+        if term_map is not None and term_map.numel() != self.n_terminals:
+            raise FdxError(f"term_map has {term_map.numel()} entries, the state {self.n_terminals} terminals")
+        ws = self._retire_ws(chunk_keys)
+        check(_lib.load().fdx_stream_retire_apply(self._h, ops._ptr(cust_map), int(cust_kept), ops._ptr(term_map),
+                                                  int(term_kept), ops._ptr(ws), ws.numel(), ops._s(stream)),
+              "fdx_stream_retire_apply")
+
     def check(self, stream=None):
         """Synchronise and raise if a kernel reported a problem since the last check."""
         f = ctypes.c_int32()
@@ -485,6 +545,41 @@ class StreamScorer:
                 self.terminals = self.terminals.resized(nt)
         self.state = new
         self.__dict__.pop("_graphs", None)
+
+    def retire_idle(self, watermark) -> dict:
+        """raw_ids: let go of the keys that can no longer influence a feature, so that their ids,
+        state rows and hash slots are reused (a cold path: hourly, daily).  watermark (int ns or
+        numpy.datetime64): the caller's promise that no row fed from here on has ts < watermark,
+        in either half, late terminal rows included (with a terminal lateness set: the next
+        batch's first ts minus the lateness).  Retired: customers idle since watermark - the
+        longest window, terminals idle since watermark - (delay + the longest window); such a key
+        that comes back is a new key and its features are bit-identical (include/fdx.h).  The
+        survivors keep their order (new id = rank), so state, snapshot() and snapshot_keys()
+        equal those of a stream fed the history without the retired keys' rows.  Waits for the
+        status of the batches so far; addresses do not move and score_graph's graphs stay valid.
+        A fraud report for a retired terminal raises like one for a terminal never seen: drop
+        reports older than watermark - (delay + the longest window) to avoid that.
+        -> {"customers": {"kept", "retired"}, "terminals": {...}}; a half in which nothing is
+        retired is not touched."""
+        self._need_raw("retire_idle")
+        st = self.state
+        st.poll(block=True)
+        import numpy as np
+
+        if isinstance(watermark, np.datetime64):
+            watermark = watermark.astype("datetime64[ns]").astype(np.int64)
+        watermark = int(watermark)
+        cmap, tmap, counts = st.retire_plan(watermark)
+        go_c = cmap is not None and counts["customers"]["retired"] > 0
+        go_t = tmap is not None and counts["terminals"]["retired"] > 0
+        if go_c or go_t:
+            st.retire_apply(cmap if go_c else None, counts["customers"]["kept"], tmap if go_t else None,
+                            counts["terminals"]["kept"])
+        if go_c:
+            self.customers.remap(cmap, counts["customers"]["kept"])
+        if go_t:
+            self.terminals.remap(tmap, counts["terminals"]["kept"])
+        return counts
 
     def _no_labels(self, n):
         """fraud = None: the batch's labels are not known yet (report_frauds brings them).  One
