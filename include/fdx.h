@@ -511,6 +511,18 @@ int fdx_forest_search_trees(const fdx_forest_desc *desc, float *trees_out, int64
  * *n_slots = rank slots.  fdx_forest_set_variant rebuilds the rank layout in another node
  * format when the requested variant needs it. */
 int fdx_forest_layout(fdx_forest forest, int32_t *layout, int32_t *n_slots);
+/* Shape of the installed rank layout's search tables (read-only; all zeros without a rank layout).
+ * A value's rank is found in two levels: among the first thresholds of every segment of *seg
+ * (16, 32 or 64) thresholds -- *n_samples of them over all features, staged into the prepare
+ * kernels' LDS: at most 8,192 for the v1 row format (layouts 1 and 3), 20,480 for layout 2 -- then
+ * inside one segment; *seg is the smallest that keeps the samples within that budget.  For a
+ * 15-feature forest in the v1 row format, features 0, 4, 6 and 8 also get the S-trees of
+ * fdx_forest_search_trees: tree_levels[s] levels each (0 for a feature without thresholds; a
+ * tree of lv levels holds 9^lv - 1 samples, one per 4 thresholds), *n_tree_floats floats in all --
+ * or 0 when the trees exceed the LDS budget and the two-level search ranks those features too
+ * (tree_levels then still tells the levels they would have needed). */
+int fdx_forest_rank_tables(fdx_forest forest, int32_t *seg, int32_t *n_samples, int32_t *n_tree_floats,
+                           int32_t tree_levels[4]);
 int fdx_forest_destroy(fdx_forest forest);
 int fdx_forest_info(fdx_forest forest, int32_t *n_trees, int32_t *n_features, int64_t *n_nodes,
                     int32_t *n_chunks);

@@ -76,9 +76,9 @@ __device__ __forceinline__ void rank_row(const float (&v)[16], int nf, const Ran
                     seg_count(std::integral_constant<int, 4>{});
                 } else if (rt.seg == 32) {
                     seg_count(std::integral_constant<int, 8>{});
-                } else if (rt.seg == 64) {  // (forests with ~300k thresholds: the deployed RF, rank layout v2)
+                } else if (rt.seg == 64) {  // (the largest: > 262,144 thresholds in v1 / v3 rows, > 655,360 in v2's)
                     seg_count(std::integral_constant<int, 16>{});
-                } else {
+                } else {  // (not reached: 15 x 32,767 / 32 x 32,767 thresholds fit 64-float segments)
                     for (int q = 0; q < rt.seg / 4; ++q) {
                         const float4 w = sg[q];
                         k += (uint32_t)(w.x < v[f]) + (uint32_t)(w.y < v[f]) + (uint32_t)(w.z < v[f]) +
@@ -1063,6 +1063,14 @@ RankTab rank_tab(const fdx_forest_s *F) {
 
 using namespace fdx;
 
+// The v1-row prepare kernels (k_prepare<16, true>, k_prepare_st, k_zfill_grouped<16, true>) stage the
+// whole sample table into s_smp[kMaxRankSamples]: install_rank_layout sizes the segments for that,
+// and every entry point that may launch one of them checks it before the launch.
+#define FDX_REQUIRE_V1_SAMPLES(F)                                                                          \
+    FDX_REQUIRE(!rank_mode(F) || (F)->rnsmp <= kMaxRankSamples,                                            \
+                "rank sample table of %d floats exceeds the v1-row kernels' LDS table (%d)", (F)->rnsmp,   \
+                kMaxRankSamples)
+
 // Launch a prepare kernel in the row format of the forest's current variant: rank rows
 // (rank layout), float32 rows of 16 or 32 slots (wide layout).
 #define FDX_PREP(KERNEL, GRID, ST, ...)                                                                    \
@@ -1099,6 +1107,7 @@ extern "C" int fdx_forest_prepare(fdx_forest F, const double *X_d, int64_t n, in
         FDX_LAUNCHED("k_prepare_v2");
         return FDX_OK;
     }
+    FDX_REQUIRE_V1_SAMPLES(F);  // k_prepare_st and k_prepare<16, true> below
     if (rank_mode(F) && F->rnetab > 0 && F->n_features == 15) {  // the S-trees of the four searched features
         const RankTab rt = rank_tab(F);
         const unsigned g = (unsigned)std::min<int64_t>(ceil_div(n, (int64_t)kPrepStBlock), (int64_t)F->n_cu * 2);
@@ -1137,6 +1146,7 @@ extern "C" int fdx_forest_prepare_features(fdx_forest F, int64_t n, int32_t n_wi
     FDX_REQUIRE(F, "null forest");
     FDX_REQUIRE(!(rank_mode(F) && v2_rows(kVariants[F->variant].p16)),
                 "the fused scoring rows need the v1 row format (one slot per feature)");
+    FDX_REQUIRE_V1_SAMPLES(F);
     FDX_REQUIRE(n >= 0 && n_windows >= 1 && n_windows <= FDX_MAX_WINDOWS, "bad argument");
     FDX_REQUIRE(F->n_features == 3 + 4 * n_windows, "forest has %d features, expected %d", F->n_features,
                 3 + 4 * n_windows);
@@ -1166,6 +1176,7 @@ extern "C" int fdx_forest_prepare_reply(fdx_forest F, const int64_t *reply_d, co
     FDX_REQUIRE(F, "null forest");
     FDX_REQUIRE(!(rank_mode(F) && v2_rows(kVariants[F->variant].p16)),
                 "the fused scoring rows need the v1 row format (one slot per feature)");
+    FDX_REQUIRE_V1_SAMPLES(F);
     FDX_REQUIRE(n >= 0 && n_windows >= 1 && n_windows <= FDX_MAX_WINDOWS, "bad argument");
     FDX_REQUIRE(col0 >= 0 && col0 + 2 * n_windows <= F->n_features, "columns out of range");
     if (n == 0) return FDX_OK;
@@ -1220,6 +1231,7 @@ extern "C" int fdx_forest_prepare_grouped(fdx_forest F, int64_t n, int32_t n_win
     FDX_REQUIRE(!rows_out_d || ((uintptr_t)rows_out_d & 15) == 0, "feature output must be 16-byte aligned");
     FDX_REQUIRE(!(rank_mode(F) && v2_rows(kVariants[F->variant].p16)),
                 "the fused scoring rows need the v1 row format (one slot per feature)");
+    FDX_REQUIRE_V1_SAMPLES(F);
     FDX_REQUIRE(n >= 0 && n_windows >= 1 && n_windows <= FDX_MAX_WINDOWS, "bad argument");
     FDX_REQUIRE(flags_mode == FDX_FLAGS_NOTEBOOK || flags_mode == FDX_FLAGS_SPARK, "bad flags mode");
     FDX_REQUIRE(F->n_features == 3 + 4 * n_windows, "forest has %d features, expected %d", F->n_features,

@@ -1231,6 +1231,17 @@ extern "C" int fdx_forest_get_variant(fdx_forest F, int32_t *variant) {
 }
 
 
+extern "C" int fdx_forest_rank_tables(fdx_forest F, int32_t *seg, int32_t *n_samples, int32_t *n_tree_floats,
+                                      int32_t tree_levels[4]) {
+    FDX_REQUIRE(F && seg && n_samples && n_tree_floats && tree_levels, "null pointer");
+    *seg = F->rank_ok ? F->rseg : 0;
+    *n_samples = F->rank_ok ? F->rnsmp : 0;
+    *n_tree_floats = F->rank_ok ? F->rnetab : 0;
+    // (the levels the S-trees need, also when they were dropped for exceeding kW3TreeFloats)
+    for (int s = 0; s < 4; ++s) tree_levels[s] = F->rank_ok ? F->relev[s] : 0;
+    return FDX_OK;
+}
+
 extern "C" int fdx_forest_layout(fdx_forest F, int32_t *layout, int32_t *n_slots) {
     FDX_REQUIRE(F && layout && n_slots, "null pointer");
     *layout = !F->rank_ok ? 0 : (F->rank_v2 ? (F->rank_identity ? 3 : 2) : 1);
@@ -1288,14 +1299,17 @@ int install_rank_layout(fdx_forest_s *F, int format, hipStream_t st) {
         F->rslot_feat[j] = RL.slot_feat[j];
         F->rslot_base[j] = RL.slot_base[j];
     }
-    // two-level search tables (RankTab): smallest segment with <= kMaxRankSamples samples
+    // two-level search tables (RankTab): smallest segment whose samples fit the LDS table of the
+    // kernels that will stage them -- k_prepare_v2's (kMaxRankSamplesV2) for v2 rows, the v1-row
+    // kernels' (kMaxRankSamples) for v1 / v3 and for an identity v2 forest, whose rows are v1's
+    const int max_smp = v2 && !F->rank_identity ? kMaxRankSamplesV2 : kMaxRankSamples;
     std::vector<float> useg, smp;
     std::vector<uint16_t> itab, rat;
     int seg = 16;
     for (;; seg *= 2) {
         int64_t m = 0;
         for (int f = 0; f < nfs; ++f) m += ceil_div(F->rthr_cnt[f], seg);
-        if (m <= (v2 ? kMaxRankSamplesV2 : kMaxRankSamples)) break;
+        if (m <= max_smp) break;
     }
     F->rseg = seg;
     for (int f = 0; f < nfs; ++f) {
@@ -1312,6 +1326,7 @@ int install_rank_layout(fdx_forest_s *F, int format, hipStream_t st) {
     // forests with the v1 row format, build_search_trees)
     std::vector<float> etab;
     F->rnetab = 0;
+    for (int s = 0; s < 4; ++s) F->reoff[s] = F->relev[s] = 0;
     if (F->n_features == 15 && seg % kW3Gap == 0 && (!v2 || F->rank_identity)) {
         build_search_trees(RL, etab, F->reoff, F->relev);
         F->rnetab = (int32_t)etab.size();

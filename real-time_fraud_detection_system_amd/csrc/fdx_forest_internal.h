@@ -136,8 +136,11 @@ struct RankTab {
     int32_t eoff[4], elev[4], n_etab;
 };
 constexpr int kW3Search[4] = {0, 4, 6, 8};  // TX_AMOUNT, CUSTOMER_ID_AVG_AMOUNT_{1,7,30}DAY_WINDOW
-constexpr int kMaxRankSamples = 8192;  // LDS sample table of the prepare kernels (32 KiB)
-// rank layout v2 (only k_prepare_v2 reads its tables): 80 KiB of samples, so that the deployed
+// LDS sample table of the v1-row prepare kernels (32 KiB): k_prepare<16, true>, k_prepare_st and
+// k_zfill_grouped<16, true> -- rank layouts v1 and v3, and a v2 forest with one slot per feature
+// (rank_identity: v2 nodes over v1 rows, prepared by those same kernels)
+constexpr int kMaxRankSamples = 8192;
+// v2 rows (32 slots; k_prepare_v2 alone stages their table): 80 KiB of samples, so that the deployed
 // model's 313k thresholds take 16-float segments (64 B per feature and row) instead of 64-float ones
 constexpr int kMaxRankSamplesV2 = 20480;
 constexpr int kW3Gap = 4;              // thresholds per S-tree sample (one 16-byte segment read)

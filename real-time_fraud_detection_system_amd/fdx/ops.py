@@ -816,6 +816,15 @@ class Forest:
         self.epoch += 1
         check(_lib.load().fdx_forest_set_range_rows(self._h, int(rows)), "fdx_forest_set_range_rows")
 
+    def rank_tables(self) -> dict:
+        """Shape of the rank search tables (fdx_forest_rank_tables): seg, n_samples, n_tree_floats and
+        tree_levels (of features 0, 4, 6, 8); zeros without a rank layout."""
+        seg, ns, nt = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        lev = (ctypes.c_int32 * 4)()
+        check(_lib.load().fdx_forest_rank_tables(self._h, ctypes.byref(seg), ctypes.byref(ns), ctypes.byref(nt), lev),
+              "fdx_forest_rank_tables")
+        return dict(seg=seg.value, n_samples=ns.value, n_tree_floats=nt.value, tree_levels=list(lev))
+
     def traverse_launches(self, n: int, want_leaves: bool = False) -> int:
         """tree-walk kernel launches of one traversal of n rows (fdx_forest_traverse_launches)"""
         k = ctypes.c_int32()

@@ -45,6 +45,19 @@ def test_error_path_without_gpu():
     assert L.fdx_rekey_workspace_size(1000, 16) > 0
 
 
+def test_rank_tables_query_refuses_null_arguments():
+    """fdx_forest_rank_tables (additive in ABI 3): a null forest or output is FDX_E_INVALID before
+    anything is read (its values on a real forest: test_gpu_rank_tables.py)."""
+    from fdx import _lib
+
+    L = _lib.load()
+    seg, ns, nt = ctypes.c_int32(7), ctypes.c_int32(7), ctypes.c_int32(7)
+    lev = (ctypes.c_int32 * 4)(7, 7, 7, 7)
+    assert L.fdx_forest_rank_tables(None, ctypes.byref(seg), ctypes.byref(ns), ctypes.byref(nt), lev) == -1
+    assert b"null" in L.fdx_last_error()
+    assert (seg.value, ns.value, nt.value, list(lev)) == (7, 7, 7, [7, 7, 7, 7])
+
+
 def test_merged_entry_points_refuse_what_the_header_rules_out():
     """fdx_rekey_payload, fdx_customer_layout, fdx_customer_layout_fill and
     fdx_terminal_windows_grouped: every combination of options include/fdx.h rules out is
