@@ -65,7 +65,17 @@ int fdx_time_flags(const int64_t *ts_ns_d, int64_t n, int32_t mode, uint8_t *wee
  *   nb_d[w*n + i]  = rolling('{w}d').count()  (int32; the reference stores it as float64)
  *   avg_d[w*n + i] = rolling('{w}d').sum() / count, bit-identical to pandas' Kahan
  *                    add/remove roll_sum (exact emulation).
- * window_ns: host array of n_windows window lengths in ns.  n = seg_off_d[n_seg]. */
+ * window_ns: host array of n_windows window lengths in ns.  n = seg_off_d[n_seg].
+ * Amounts: any float64.  NaN is left out of count and sum; +-inf is counted and left out of the
+ * sum, as pandas does (rolling sum() turns it into NaN before roll_sum, count() still counts
+ * it), so avg is the finite sum over a count that includes the infinities.
+ * The amount contract of every other entry point that runs the recurrence -- the layout kernels
+ * (fdx_customer_windows_interleaved, fdx_customer_windows_walk[_strided]), the row assembly,
+ * fdx_stream_update, and the pipelines built on them (run_fused, streaming): finite or NaN
+ * amounts, bit-identical to pandas and to this call; an infinite amount there follows IEEE
+ * arithmetic (it enters the sum, inf - inf = NaN stays until the window re-initialises), not
+ * pandas.  The scan mode (fdx_customer_windows_scan*) is not exact and takes finite or NaN
+ * amounts only. */
 int fdx_customer_windows(const int64_t *ts_ns_d, const double *amount_d, const int64_t *seg_off_d,
                          int64_t n_seg, int64_t n, const int64_t *window_ns, int32_t n_windows,
                          int32_t *nb_d, double *avg_d, void *stream);

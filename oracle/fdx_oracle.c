@@ -15,7 +15,9 @@
  *    DatetimeIndex: pandas/_libs/window/indexers.pyx calculate_variable_window_bounds
  *    (closed='right') + pandas/_libs/window/aggregations.pyx roll_sum / add_sum /
  *    remove_sum / calc_sum (Kahan add/remove with separate compensations, reset when the
- *    new window does not overlap the previous one, "n consecutive equal values" rule).
+ *    new window does not overlap the previous one, "n consecutive equal values" rule);
+ *    pandas/core/window/rolling.py _prep_values (+-inf -> NaN ahead of every aggregation
+ *    but count, which still counts it).
  *    Called from fraud_detection_model/feature_transformation.ipynb:613-614
  *    (customer) and :1501-1502, :1506-1507 (terminal).
  *  - scikit-learn 1.6.1 (poetry.lock:2248-2250) StandardScaler.transform
@@ -93,8 +95,13 @@ static void variable_bounds(const int64_t *t, int64_t n, int64_t w, int64_t *sta
     }
 }
 
-/* roll_sum over one segment; also returns the rolling count of non-NaN values
- * (Rolling.count = rolling sum of notna(), an exact integer). */
+/* Rolling.sum's _prep_values turns +-inf into NaN before roll_sum sees the values, so an
+ * infinite value is left out of the sum (and of nobs, prev and the equal-values rule). */
+static double sum_input(double v) { return isinf(v) ? NAN : v; }
+
+/* roll_sum over one segment; also returns the rolling count (Rolling.count = rolling sum of
+ * notna(), an exact integer): NaN is left out, +-inf is counted.  So with an infinity in the
+ * window, sum / count is the finite sum over a count that includes the infinity. */
 static void roll_sum_count(const double *v, const int64_t *start, const int64_t *end, int64_t n,
                            double *sum_out, double *cnt_out) {
     rsum_t s;
@@ -102,12 +109,12 @@ static void roll_sum_count(const double *v, const int64_t *start, const int64_t 
     for (int64_t i = 0; i < n; i++) {
         int64_t st = start[i], en = end[i];
         if (i == 0 || st >= end[i - 1]) {
-            rs_reset(&s, v[st]);
+            rs_reset(&s, sum_input(v[st]));
             cnt = 0;
-            for (int64_t j = st; j < en; j++) { rs_add(&s, v[j]); cnt += (v[j] == v[j]); }
+            for (int64_t j = st; j < en; j++) { rs_add(&s, sum_input(v[j])); cnt += (v[j] == v[j]); }
         } else {
-            for (int64_t j = start[i - 1]; j < st; j++) { rs_remove(&s, v[j]); cnt -= (v[j] == v[j]); }
-            for (int64_t j = end[i - 1]; j < en; j++) { rs_add(&s, v[j]); cnt += (v[j] == v[j]); }
+            for (int64_t j = start[i - 1]; j < st; j++) { rs_remove(&s, sum_input(v[j])); cnt -= (v[j] == v[j]); }
+            for (int64_t j = end[i - 1]; j < en; j++) { rs_add(&s, sum_input(v[j])); cnt += (v[j] == v[j]); }
         }
         /* rolling offset windows default to min_periods=1 */
         if (sum_out) sum_out[i] = rs_value(&s, 1);

@@ -411,7 +411,7 @@ __global__ void __launch_bounds__(256) k_zfill_grouped(
                     const int32_t c = cnb[(int64_t)w * n + i];
                     const double cv = cval[(int64_t)w * n + i];
                     count(3 + 2 * w, c);
-                    v[4 + 2 * w] = zval((val_is_sum & 1) ? cv / (double)c : cv, mean, scale, 4 + 2 * w);
+                    v[4 + 2 * w] = zval((val_is_sum & 1) ? div_count(cv, (double)c) : cv, mean, scale, 4 + 2 * w);
                     const int64_t tw = (val_is_sum & 4) ? ctw[w < 3 ? w : 0] : rec[w];
                     const int32_t tnb = term_nb(tw), tfr = (int32_t)((uint64_t)tw >> 32);
                     count(3 + 2 * W + 2 * w, tnb);
@@ -462,7 +462,7 @@ __global__ void __launch_bounds__(256) k_zfill_grouped(
                 const int32_t c = cnb[(int64_t)w * n + i];
                 const double cv = cval[(int64_t)w * n + i];
                 v[3 + 2 * w] = zval((double)c, mean, scale, 3 + 2 * w);
-                v[4 + 2 * w] = zval((val_is_sum & 1) ? cv / (double)c : cv, mean, scale, 4 + 2 * w);
+                v[4 + 2 * w] = zval((val_is_sum & 1) ? div_count(cv, (double)c) : cv, mean, scale, 4 + 2 * w);
                 const int64_t tw = (val_is_sum & 4) ? ctw[w < 3 ? w : 0] : rec[w];
                 v[3 + 2 * W + 2 * w] = zval((double)term_nb(tw), mean, scale, 3 + 2 * W + 2 * w);
                 v[4 + 2 * W + 2 * w] = zval(term_risk(tw), mean, scale, 4 + 2 * W + 2 * w);
@@ -806,7 +806,7 @@ __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
 #pragma unroll
                 for (int w = 0; w < W; ++w) {
                     c[w] = live ? (uint32_t)cur.c[w] : 0u;
-                    avg[w] = !live ? 0.0 : is_sum ? cur.cv[w] / (double)cur.c[w] : cur.cv[w];
+                    avg[w] = !live ? 0.0 : is_sum ? div_count(cur.cv[w], (double)cur.c[w]) : cur.cv[w];
                     tn[w] = live ? (uint32_t)term_nb(cur.tw[w]) : 0u;
                     rk[w] = live ? term_risk(cur.tw[w]) : 0.0;
                 }
@@ -859,7 +859,7 @@ __global__ void __launch_bounds__(kW3Block) k_zfill_grouped_w3(
         for (int w = 0; w < W; ++w) {
             const int32_t c = cur.c[w];
             count(3 + 2 * w, c);
-            v[4 + 2 * w] = zs(is_sum ? cur.cv[w] / (double)c : cur.cv[w], 4 + 2 * w);
+            v[4 + 2 * w] = zs(is_sum ? div_count(cur.cv[w], (double)c) : cur.cv[w], 4 + 2 * w);
             nan |= v[4 + 2 * w] != v[4 + 2 * w];
             const int64_t tw = cur.tw[w];
             const int32_t tnb = term_nb(tw), tfr = (int32_t)((uint64_t)tw >> 32);
@@ -986,7 +986,7 @@ __global__ void __launch_bounds__(256) k_feature_rows(
                 const int32_t cw = cnb[(int64_t)w * n + i];
                 const double cv = cval[(int64_t)w * n + i];
                 c[w] = (uint32_t)cw;
-                avg[w] = (val_is_sum & 1) ? cv / (double)cw : cv;
+                avg[w] = (val_is_sum & 1) ? div_count(cv, (double)cw) : cv;
                 tn[w] = (uint32_t)term_nb(tw[w]);
                 rk[w] = term_risk(tw[w]);
             }

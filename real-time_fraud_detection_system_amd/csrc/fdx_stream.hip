@@ -184,7 +184,7 @@ __device__ void customer_key(int32_t c, int32_t head, const int32_t *__restrict_
                 csum_out[(int64_t)w * n_rows + row] = s[w].value();
             } else {
                 x[2 * w] = (double)s[w].nobs;
-                x[2 * w + 1] = s[w].value() / (double)s[w].nobs;
+                x[2 * w + 1] = div_count(s[w].value(), (double)s[w].nobs);
             }
         }
         if (n >= C && n - C >= tmin) bad |= kStCustRing;

@@ -88,30 +88,41 @@ __global__ void __launch_bounds__(256) k_customer_exact(
     int32_t *nb = nb_out + (int64_t)wi * n;
     double *avg = avg_out + (int64_t)wi * n;
 
+    // An infinite amount: pandas' rolling sum turns it into NaN before roll_sum (so the sum, nobs
+    // and the equal-values rule leave it out) while rolling count still counts it; ninf = the
+    // infinities in the window, beside the roll_sum state.
+    const auto sum_input = [](double x) { return __builtin_isinf(x) ? __builtin_nan("") : x; };
     RollSum s;
+    int32_t ninf = 0;
     int64_t tail = b;
     for (int64_t i = b; i < e; ++i) {
         const int64_t t = ts[i];
-        const double v = amount[i];
+        const double a = amount[i], v = sum_input(a);
         if (i == b) {
             s.reset(v);
-            s.add(v);
+            ninf = 0;
         } else {
             const int64_t bound = t - W;
             int64_t nt = tail;
             while (nt < i && ts[nt] <= bound) ++nt;
             if (nt >= i) {  // start[i] >= end[i-1]: pandas re-initialises the window
                 s.reset(v);
-                s.add(v);
+                ninf = 0;
             } else {
-                for (int64_t j = tail; j < nt; ++j) s.remove(amount[j]);
-                s.add(v);
+                for (int64_t j = tail; j < nt; ++j) {
+                    const double r = amount[j];
+                    s.remove(sum_input(r));
+                    ninf -= __builtin_isinf(r) ? 1 : 0;
+                }
             }
             tail = nt;
         }
+        s.add(v);
+        ninf += __builtin_isinf(a) ? 1 : 0;
         const double sum = s.value();
-        nb[i] = s.nobs;
-        avg[i] = sum / (double)s.nobs;
+        const int32_t cnt = s.nobs + ninf;
+        nb[i] = cnt;
+        avg[i] = div_count(sum, (double)cnt);
     }
 }
 
@@ -977,7 +988,7 @@ __global__ void __launch_bounds__(64) k_customer_walk(
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         if constexpr (Out::kAvg) {  // (a lane past its segment's end divides stale values: never stored)
 #pragma unroll
-            for (int j = 0; j < kChunk; ++j) oval[j] = oval[j] / (double)onb[j];
+            for (int j = 0; j < kChunk; ++j) oval[j] = div_count(oval[j], (double)onb[j]);
         }
         if constexpr (BUF) {
             const uint32_t o0 = (uint32_t)((int64_t)wi * nbs + gbase + seg0 + l);  // element index of row 0

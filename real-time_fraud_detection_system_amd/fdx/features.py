@@ -110,8 +110,10 @@ def get_customer_spending_behaviour_features(customer_transactions: pd.DataFrame
                                              windows_size_in_days: Sequence[int] = (1, 7, 30),
                                              mode: str = "exact"):
     """feature_transformation.ipynb:601-628 for one or many customers at once.  mode="exact":
-    pandas' roll_sum bit for bit; mode="scan": float64 prefix sums (counts exact, averages
-    within ~1e-13 relative)."""
+    pandas' roll_sum bit for bit, for any float64 amount -- NaN is left out of count and sum, +-inf
+    is counted and left out of the sum, as pandas' rolling count() and sum() do; mode="scan":
+    float64 prefix sums (counts exact, averages within ~1e-13 relative), which
+    an infinite amount would poison for the rest of its segment: ValueError."""
     if mode not in ("exact", "scan"):
         raise ValueError("mode must be 'exact' or 'scan'")
     dev = ops.require_gpu()
@@ -119,8 +121,13 @@ def get_customer_spending_behaviour_features(customer_transactions: pd.DataFrame
     if len(df) == 0:  # pandas' groupby.apply of an empty frame: no rows, the new columns
         return _empty_out(df, [f"CUSTOMER_ID_{k}_{w}DAY_WINDOW" for w in windows_size_in_days
                                for k in ("NB_TX", "AVG_AMOUNT")])
+    amt = df["TX_AMOUNT"].values.astype(np.float64)
+    # (this function alone refuses: ops.customer_windows_scan and FraudPipeline(avg_mode="scan") take
+    # finite or NaN amounts by contract, include/fdx.h, and do not look)
+    if mode == "scan" and np.isinf(amt).any():
+        raise ValueError("mode='scan' does not take infinite amounts (mode='exact' follows pandas on them)")
     perm, seg, ts_d = _grouped_order(df, "CUSTOMER_ID", dev)
-    amt_d = _to_dev(df["TX_AMOUNT"].values.astype(np.float64), torch.float64, dev)
+    amt_d = _to_dev(amt, torch.float64, dev)
     if mode == "scan":
         nb, avg = ops.customer_windows_scan(ops.gather(ts_d, perm), ops.gather(amt_d, perm), seg,
                                             windows_size_in_days)
