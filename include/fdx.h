@@ -220,7 +220,11 @@ int fdx_terminal_windows(const int64_t *ts_ns_d, const uint8_t *fraud_d, const i
  * amount/weekend/night are in output row order; the grouped outputs of
  * fdx_customer_windows / fdx_terminal_windows are scattered back through their perms.
  * The three term_* pointers may all be NULL (the multi-GPU path fills those columns with
- * fdx_reply_assemble after the return exchange). */
+ * fdx_reply_assemble after the return exchange): the terminal columns, like the columns from
+ * 3 + 4*n_windows to ld, then keep their bytes.
+ * cust_perm_d / term_perm_d are PLAIN row indices in [0, n) (fdx_rekey's perm): the kernels index
+ * X_d with them as they are, bit 31 is not masked -- fdx_rekey_payload's flag-packed perm
+ * (flag_d given) must have its bit 31 cleared first. */
 int fdx_assemble_features(int64_t n, int32_t n_windows, const double *amount_d,
                           const uint8_t *weekend_d, const uint8_t *night_d, const int32_t *cust_perm_d,
                           const int32_t *cust_nb_d, const double *cust_avg_d, const int32_t *term_perm_d,
@@ -371,7 +375,6 @@ int fdx_dense_ids_i64(const int64_t *keys_d, int64_t n, int32_t *ids_d, int64_t 
 /* *flag_d = 1 if keys_d is non-decreasing, else 0 (stream-ordered). */
 int fdx_is_sorted_i64(const int64_t *keys_d, int64_t n, int32_t *flag_d, void *stream);
 
-/* Device-wide exclusive prefix sum of m uint32 values, in place. */
 /* seg_off_d[0..n_keys] of the stable grouping by key -- equal to fdx_rekey's seg_off when every
  * key lies in [0, n_keys) -- from a key histogram, without sorting (the group sizes of
  * groupby('CUSTOMER_ID'), feature_transformation.ipynb:1092; the customer layout's plan needs
@@ -381,6 +384,9 @@ size_t fdx_key_segments_workspace_size(int64_t n_keys);
 int fdx_key_segments(const int32_t *keys_d, int64_t n, int64_t n_keys, int64_t *seg_off_d, int32_t *bad_d,
                      void *workspace_d, size_t workspace_bytes, void *stream);
 
+/* Device-wide exclusive prefix sum of m uint32 values, in place: data_d[i] becomes the sum of
+ * the values before position i, modulo 2^32 (sums wrap).  workspace_d: fdx_exclusive_scan_u32_workspace_size(m)
+ * bytes; nothing behind them, and nothing behind the m words, is written.  m = 0 does nothing. */
 size_t fdx_exclusive_scan_u32_workspace_size(int64_t m);
 int fdx_exclusive_scan_u32(uint32_t *data_d, int64_t m, void *workspace_d, void *stream);
 
@@ -589,7 +595,16 @@ int fdx_forest_set_range_rows(fdx_forest forest, int64_t rows);
  * rows in the workspace straight from the window kernels' grouped outputs (same columns
  * and arithmetic as fdx_assemble_features followed by fdx_forest_prepare), so
  * fdx_forest_traverse can follow.  term_* may be NULL (filled by fdx_forest_prepare_reply
- * in the multi-GPU path, col0 = 3 + 2*n_windows). */
+ * in the multi-GPU path, col0 = 3 + 2*n_windows).
+ *   The perms of both calls (cust_perm_d, term_perm_d, perm_d) are PLAIN row indices in [0, n):
+ * the kernels index the rows with them as they are, bit 31 is not masked -- not
+ * fdx_rekey_payload's flag-packed perm.  reply_d: count records, n_windows words per row j, row
+ * j belonging to transaction perm_d[j].
+ *   Refused with FDX_E_INVALID, before anything is written: a forest whose feature count is not
+ * 3 + 4*n_windows (prepare_features), col0 < 0 or col0 + 2*n_windows beyond the feature count
+ * (prepare_reply), and a forest in the v2 row format (several slots per feature: fdx_forest_layout
+ * 2).  A workspace without the room fdx_forest_workspace_size(forest, n) gives the rows and
+ * running sums (all of it for a forest of one chunk): FDX_E_WORKSPACE, nothing written. */
 int fdx_forest_prepare_features(fdx_forest forest, int64_t n, int32_t n_windows,
                                 const double *amount_d, const uint8_t *weekend_d,
                                 const uint8_t *night_d, const int32_t *cust_perm_d,
